@@ -96,7 +96,36 @@ def parse():
                     help="the timed region (--steps steps between barriers) is run this many times; the median is reported")
     ap.add_argument("--settle-seconds", type=float, default=0.4,
                     help="untimed replays after the --warmup steps until the GPU has been busy this long (clocks, graph upload)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="default mode: after the timed region, write what its last step computed (every layer's z_new and logsd, "
+                         "stacked per latent level) to DIR/<name>.npy in float32, at most 64 MB in all (a fixed seeded sample beyond)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.train or args.layers or args.model or args.iw_eval):
+        ap.error("--dump-outputs writes the default workload's outputs; it does not combine with --train, --layers, --model or --iw-eval")
+    return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, layers):
+    """--dump-outputs: the arrays a caller of the timed step receives -- each layer's (z_new, logsd) of iaf_step -- as
+    <name>_<H>x<W>.npy, [layers, B, n_z, H, W] float32.  Beyond DUMP_BYTES in all, every array is cut to the same share of its
+    elements at fixed seeded positions (flat, ascending), so that two runs with the same arguments still compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for H in sorted({L["H"] for L in layers}, reverse=True):
+        lv = [L for L in layers if L["H"] == H]
+        for i, name in enumerate(("z_new", "logsd")):
+            arrays["%s_%dx%d" % (name, H, H)] = torch.stack([L["out"][i] for L in lv]).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 RANK_INFO = {}
@@ -1491,6 +1520,8 @@ def main():
             barrier()
             repeats.append(time.perf_counter() - t0)
         elapsed = float(np.median(repeats))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, layers)      # before the kernel leg below launches these layers again
 
         # ---------------- kernel leg: eager steps, HIP events around every launch of the dominant kernel
         # IN SITU per launch (VERDICT r03 "next" #5: a relaunched layer meets its 0.8-1.2 MB of weight packs L2-hot and reads

@@ -228,6 +228,24 @@ def lib():
     return _lib
 
 
+_deferred = []      # (native destructor, handle) put off by destroy() while the current stream was capturing
+
+
+def destroy(name, handle):
+    """Call the native destructor `name` on `handle` from a finaliser.  The destructors free device memory, and a hipFree while a
+    stream capture runs invalidates that capture (torch.cuda.graph captures in global mode and no longer collects garbage before
+    it begins, so Python's cyclic GC may finalise an engine object in the middle of one).  During a capture on the current stream
+    the call is put off; the first destroy() outside a capture makes the calls put off before its own, in their order."""
+    import torch
+    if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():
+        _deferred.append((name, handle))
+        return
+    while _deferred:
+        n, h = _deferred.pop(0)
+        getattr(lib(), n)(h)
+    getattr(lib(), name)(handle)
+
+
 def error_string(code):
     return lib().iaf_error_string(int(code)).decode()
 

@@ -75,7 +75,8 @@ def build(force=False, verbose=True, jobs=None):
         if force or _stale(obj, _deps(obj, src)):
             todo.append([hipcc] + CFLAGS + defs + ["-MD", "-MF", obj + ".d", "-c", src, "-o", obj])
     if todo:
-        jobs = jobs or min(len(todo), os.cpu_count() or 4)
+        # MAX_JOBS: the CPUs this process may use, where os.cpu_count() reports a larger shared host
+        jobs = jobs or min(len(todo), int(os.environ.get("MAX_JOBS") or 0) or os.cpu_count() or 4)
         if verbose:
             print("compiling %d translation unit(s) for gfx950 with %d job(s)" % (len(todo), jobs), flush=True)
         with concurrent.futures.ThreadPoolExecutor(jobs) as ex:

@@ -143,7 +143,7 @@ class ARStack(object):
         h, self._h = getattr(self, "_h", None), None
         if h:
             try:
-                _capi.lib().iaf_stack_destroy(h)
+                _capi.destroy("iaf_stack_destroy", h)
             except Exception:
                 pass
 
@@ -616,7 +616,7 @@ class WNConv2d(object):
         h, self._h = getattr(self, "_h", None), None
         if h:
             try:
-                _capi.lib().iaf_conv3x3_destroy(h)
+                _capi.destroy("iaf_conv3x3_destroy", h)
             except Exception:
                 pass
 
@@ -937,7 +937,7 @@ class PrepBatch(object):
         h, self._h = getattr(self, "_h", None), None
         if h:
             try:
-                _capi.lib().iaf_prep_batch_destroy(h)
+                _capi.destroy("iaf_prep_batch_destroy", h)
             except Exception:
                 pass
 
@@ -970,7 +970,7 @@ class ConvPrepBatch(object):
         h, self._h = getattr(self, "_h", None), None
         if h:
             try:
-                _capi.lib().iaf_conv3x3_prep_batch_destroy(h)
+                _capi.destroy("iaf_conv3x3_prep_batch_destroy", h)
             except Exception:
                 pass
 
@@ -1017,11 +1017,10 @@ class WnBwdBatch(object):
 
     def __del__(self):
         try:
-            lib = _capi.lib()
             if getattr(self, "_hs", None):
-                lib.iaf_wn_bwd_batch_destroy(self._hs)
+                _capi.destroy("iaf_wn_bwd_batch_destroy", self._hs)
             if getattr(self, "_hc", None):
-                lib.iaf_conv3x3_wn_bwd_batch_destroy(self._hc)
+                _capi.destroy("iaf_conv3x3_wn_bwd_batch_destroy", self._hc)
         except Exception:
             pass
 

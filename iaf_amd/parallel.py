@@ -52,7 +52,7 @@ class RcclComm(object):
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            self._capi.lib().iaf_comm_destroy(self._h)
+            self._capi.destroy("iaf_comm_destroy", self._h)
             self._h = None
 
     def __del__(self):

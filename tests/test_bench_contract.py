@@ -127,3 +127,66 @@ def test_profile_json_matches_the_csv_it_cites():
     pj = json.load(open(os.path.join(ROOT, "profiles", "pmc_dominant_kernel.json")))
     rp = re.search(r"profiles/(r\d+)/pmc/", pj["command"])
     assert rp and json.load(open(os.path.join(ROOT, "profiles", rp.group(1), "pmc_dominant_kernel.json"))) == pj
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_writes_every_layer_and_samples_beyond_the_budget(tmp_path, monkeypatch):
+    """CPU: --dump-outputs stacks each latent level's (z_new, logsd) into float32 .npy files; past the byte budget every array keeps
+    the same share of its elements at the same seeded positions, so two runs with the same arguments compare element for element"""
+    import numpy as np
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    layers = [dict(H=H, out=(torch.randn(3, 4, H, H, generator=g), torch.randn(3, 4, H, H, generator=g))) for H in (16, 16, 8)]
+    bench.dump_outputs(str(tmp_path / "full"), layers)
+    for name, i, lv in (("z_new", 0, layers[:2]), ("logsd", 1, layers[:2]), ("z_new", 0, layers[2:]), ("logsd", 1, layers[2:])):
+        H = lv[0]["H"]
+        a = np.load(str(tmp_path / "full" / ("%s_%dx%d.npy" % (name, H, H))))
+        assert a.dtype == np.float32 and a.shape == (len(lv), 3, 4, H, H)
+        assert np.array_equal(a, torch.stack([L["out"][i] for L in lv]).numpy())
+    assert sorted(os.listdir(str(tmp_path / "full"))) == ["logsd_16x16.npy", "logsd_8x8.npy", "z_new_16x16.npy", "z_new_8x8.npy"]
+    total = sum(os.path.getsize(str(tmp_path / "full" / f)) for f in os.listdir(str(tmp_path / "full")))
+    monkeypatch.setattr(bench, "DUMP_BYTES", total // 4)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), layers)
+    for f in os.listdir(str(tmp_path / "full")):
+        full, a, b = (np.load(str(tmp_path / d / f)) for d in ("full", "a", "b"))
+        assert a.ndim == 1 and 0 < a.size < full.size // 3 and np.array_equal(a, b)
+        assert np.isin(a, full.reshape(-1)).all()
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))) <= total // 4 + 4 * 128
+
+
+def test_steps_below_one_and_dump_outputs_outside_the_default_mode_are_refused(tmp_path):
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr and not r.stdout.strip()
+    r = _run(["--train", "--dump-outputs", str(tmp_path)])
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not os.listdir(str(tmp_path))
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_what_the_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: after the timed steps, every layer's z_new and logsd as the caller of the step receives them; the first
+    16x16 layer (bench.py's seeded inputs) against the CPU oracle"""
+    import numpy as np
+    from oracle import iaf_oracle as O
+    bench = _bench_module()
+    r = _run(["--steps", "3", "--warmup", "1", "--repeats", "1", "--settle-seconds", "0", "--depths", "2,2", "--no-cpu-baseline",
+              "--no-modes", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert sorted(got) == ["logsd_16x16", "logsd_8x8", "z_new_16x16", "z_new_8x8"]
+    for k, a in got.items():
+        H = int(k.split("_")[-1].split("x")[0])
+        assert a.dtype == np.float32 and a.shape == (2, 32, 32, H, H) and np.isfinite(a).all(), k
+    params, z, ctx = bench.make_layer_inputs(np.random.RandomState(1234), 32, 32, 160, 2, 16)
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    ez, es = O.iaf_step(f32(z), f32(ctx), {k: f32(v) for k, v in params.items()}, [160, 160])
+    assert np.abs(got["z_new_16x16"][0] - ez).max() < 1e-4 and np.abs(got["logsd_16x16"][0] - es).max() < 1e-4

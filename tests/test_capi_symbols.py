@@ -84,3 +84,29 @@ def test_product_never_imports_oracle():
             if f.endswith((".py", ".hip", ".hpp", ".h")):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert "oracle" not in txt.replace("no CPU fallback", ""), "%s mentions the oracle" % f
+
+
+def test_destroy_is_put_off_while_the_current_stream_captures(monkeypatch):
+    """a finaliser's native destructor frees device memory, which would invalidate a capture in progress: _capi.destroy puts the call
+    off while the current stream captures and makes it, in order, at the first destroy outside a capture"""
+    import types
+    import torch
+    from iaf_amd import _capi
+    calls = []
+    fake = types.SimpleNamespace(iaf_stack_destroy=lambda h: calls.append(("stack", h)),
+                                 iaf_conv3x3_destroy=lambda h: calls.append(("conv", h)))
+    capturing = [True]
+    monkeypatch.setattr(_capi, "lib", lambda: fake)
+    monkeypatch.setattr(_capi, "_deferred", [])
+    monkeypatch.setattr(torch.cuda, "is_initialized", lambda: True)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: capturing[0])
+    _capi.destroy("iaf_stack_destroy", 1)
+    _capi.destroy("iaf_conv3x3_destroy", 2)
+    assert calls == [] and len(_capi._deferred) == 2
+    capturing[0] = False
+    _capi.destroy("iaf_stack_destroy", 3)
+    assert calls == [("stack", 1), ("conv", 2), ("stack", 3)] and _capi._deferred == []
+    monkeypatch.setattr(torch.cuda, "is_initialized", lambda: False)      # no CUDA context: no capture can run, nothing to ask
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: 1 / 0)
+    _capi.destroy("iaf_conv3x3_destroy", 4)
+    assert calls[-1] == ("conv", 4)

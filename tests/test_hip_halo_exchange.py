@@ -291,3 +291,42 @@ def test_a_capture_takes_over_the_set_it_was_not_warmed_up_on(amd):
     xs.set_halo_exchange_debug(0)
     xs.set_halo_exchange(True)
     assert xs.exchange_errors() == 0
+
+
+def test_an_engine_object_collected_during_a_capture_does_not_invalidate_it(amd):
+    """torch.cuda.graph no longer collects garbage before it captures, so Python's cyclic GC may finalise an engine object left in a
+    reference cycle (an earlier test's stack, held by a traceback) in the middle of a capture, where its destructor's hipFree would
+    invalidate the capture (global mode): the destructor is put off until no capture runs (iaf_amd/_capi.py, destroy)"""
+    import gc
+    from iaf_amd import _capi
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        gc.collect()
+        xs, rc = _stacks(amd, 32, [160, 160], 23)
+        dead, _ = _stacks(amd, 32, [160, 160], 29)               # prepared: it holds device memory
+        dead_h = dead._h
+        dead.cycle = dead
+        del dead, _
+        g = torch.Generator(device="cuda").manual_seed(37)
+        z = torch.randn(32, 32, 16, 16, device="cuda", generator=g)
+        ctx = torch.randn(32, 160, 16, 16, device="cuda", generator=g)
+        xs.iaf_step(z, ctx)                                      # warm-up on the current stream
+        torch.cuda.synchronize()
+        out = (torch.empty_like(z), torch.empty_like(z))
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            xs.iaf_step(z, ctx, out=out)
+            gc.collect()                                         # the stack in the cycle is finalised here, inside the capture
+            assert any(h is dead_h for _, h in _capi._deferred)
+        graph.replay()
+        zr, sr = rc.iaf_step(z, ctx)
+        torch.cuda.synchronize()
+        _close(out[0], zr, "replayed z")
+        _close(out[1], sr, "replayed logsd")
+        tmp = amd.ARStack(32, [160, 160])
+        del tmp                                                  # the next destroy outside a capture makes the call put off
+        assert not _capi._deferred
+    finally:
+        if was_enabled:
+            gc.enable()
