@@ -488,6 +488,20 @@ static int conv3x3_launch(GemmLayer& L, ConvP& p, int epi_sel, int inmode, bool 
     return (int)hipGetLastError();
 }
 
+// an F16 launch of this conv (or the prep of its pack) met an operand beyond fp16's range: said once (true: the caller returns IAF_ERR_RANGE);
+// bf16x3 from here on
+static bool conv_range_report(iaf_conv3x3* c) {
+    if (c->precision == IAF_PRECISION_F16X2 && !c->f16_off && c->rng_err_host && *(volatile unsigned*)c->rng_err_host) {
+        c->f16_off = true;
+        if (!(c->packs & IAF_PACK_BF16X3)) {           // (iaf_conv3x3_set_packs: the bf16x3 pack was not kept up to date -- every pack from the next prepare on)
+            c->packs = IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2;
+            c->prepared = false;
+        }
+        return true;
+    }
+    return false;
+}
+
 extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float* x2, int c_split, int elu_input,
                                    const float* residual, float* const* outs, const int* out_channels, int n_outs, int B,
                                    int H, int W, void* stream) {
@@ -530,15 +544,7 @@ extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float
         p.split_end[k] = ends[k < n_outs ? k : n_outs - 1];
         p.split_ptr[k] = outs[k < n_outs ? k : n_outs - 1];
     }
-    // an F16 launch of this conv (or the prep of its pack) met an operand beyond fp16's range: said once; bf16x3 from here on
-    if (c->precision == IAF_PRECISION_F16X2 && !c->f16_off && c->rng_err_host && *(volatile unsigned*)c->rng_err_host) {
-        c->f16_off = true;
-        if (!(c->packs & IAF_PACK_BF16X3)) {           // (iaf_conv3x3_set_packs: the bf16x3 pack was not kept up to date -- every pack from the next prepare on)
-            c->packs = IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2;
-            c->prepared = false;
-        }
-        return IAF_ERR_RANGE;
-    }
+    if (conv_range_report(c)) return IAF_ERR_RANGE;
     if (!c->mask_mode && c->packs != (IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2)) {
         // iaf_conv3x3_set_packs: the pack this launch reads must be one the prep launches write
         GemmLayer t = L;
@@ -549,6 +555,70 @@ extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float
     }
     return conv3x3_launch(L, p, c->mask_mode ? EPI_PLAIN5 : EPI_PLAIN, IN_NCHW, c->mask_mode != 0, false, st, c->variant,
                           (conv_split(c) && !c->deconv) ? c->bf3_choice : 3, conv_f16_active(c) ? c->rng_err_dev : nullptr);
+}
+
+// ---- down_conv1 in prior form: the sample-mode top-down pass (tf_train.py:52-54, 56, 60-61; iaf_conv_bf3.hpp EPI_PRIOR) -------------
+// Only the co tiles mode "sample" reads -- pz_mean, pz_logsd, h_det: (2 n_z + n_h) / 16 of down_conv1's (4 n_z + 2 n_h) / 16 -- stream from the
+// conv's own pack (launch tile -> pack tile map, prior_pack_tile), and the prior sample is drawn in the epilogue.  Launch shape: the plain
+// conv's size rule (fewest workgroups per 32-pixel block that still fill the chip, at most an eighth of the tiles ragged) on the LAUNCHED
+// tiles, with NT in {2, 4} (two-tile units).  Arithmetic: two fp16 planes where the forward at this size runs them
+// (iaf_conv3x3_runs_f16x2, same range word and protocol), else the bf16x3 planes at any size (fp32-grade; there is no fp32-kernel form).
+static conv_fn_t conv3x3_prior_shape(const GemmLayer& L, int nlt, long long P, int W, bool f16, int* nt_out, int* wco_out, size_t* lds_out) {
+    static const int cand[6][2] = {{4, 3}, {4, 2}, {2, 3}, {4, 1}, {2, 2}, {2, 1}};
+    const long long nblk = (P + 31) / 32;
+    int best = -1;
+    long long best_wgs = 0;
+    for (int i = 0; i < 6; ++i) {
+        const int nt = cand[i][0], wco = cand[i][1], per = nt * wco;
+        const int covered = (nlt + per - 1) / per * per;
+        if ((covered - nlt) * 8 > nlt || !pick_bf3_prior(nt, 2, 1, 4, wco, f16 ? 1 : 0)) continue;
+        if (bf3_plain_lds_bytes(L.cin, W, nt, 2, 1, 4, wco, f16 ? 2 : 3) > 160 * 1024) continue;
+        const long long wgs = nblk * (covered / per);
+        if (wgs >= 256) { best = i; break; }
+        if (wgs > best_wgs) { best_wgs = wgs; best = i; }
+    }
+    if (best < 0) return nullptr;
+    *nt_out = cand[best][0]; *wco_out = cand[best][1];
+    *lds_out = bf3_plain_lds_bytes(L.cin, W, *nt_out, 2, 1, 4, *wco_out, f16 ? 2 : 3);
+    return pick_bf3_prior(*nt_out, 2, 1, 4, *wco_out, f16 ? 1 : 0);
+}
+
+extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, const float* eps, float* z,
+                                                float* h_det, int B, int H, int W, void* stream) {
+    if (!c || !x || !eps || !z || !h_det) return IAF_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || n_z <= 0 || n_h <= 0) return IAF_ERR_SHAPE;
+    if ((long long)B * H * W > (1LL << 30) / 64) return IAF_ERR_SHAPE;
+    if (c->n_out != 4 * n_z + 2 * n_h) return IAF_ERR_SHAPE;
+    GemmLayer& L = c->L;
+    if (c->generic || c->mask_mode || c->deconv || !L.wp3 || !conv_split(c) || (n_z & 15) || (n_h & 15)) return IAF_ERR_UNSUPPORTED;
+    if (!c->prepared) return IAF_ERR_NOT_PREPARED;
+    if (conv_range_report(c)) return IAF_ERR_RANGE;
+    const bool f16 = iaf_conv3x3_runs_f16x2(c, B, H, W) != 0;
+    if (!(c->packs & (f16 ? IAF_PACK_F16X2 : IAF_PACK_BF16X3))) return IAF_ERR_NOT_PREPARED;    // (iaf_conv3x3_set_packs)
+    ConvP p;
+    memset(&p, 0, sizeof(p));
+    p.pr_nzt = n_z / 16; p.pr_nht = n_h / 16; p.pr_nlt = 2 * p.pr_nzt + 2 * ((p.pr_nht + 1) / 2);
+    int nt = 0, wco = 0;
+    size_t lds = 0;
+    conv_fn_t fn = conv3x3_prior_shape(L, p.pr_nlt, (long long)B * H * W, W, f16, &nt, &wco, &lds);
+    if (!fn) return IAF_ERR_UNSUPPORTED;
+    p.B = B; p.H = H; p.W = W; p.HW = H * W; p.P = B * H * W;
+    p.x = x; p.in_elu = elu_input ? 1 : 0;
+    p.eps = eps; p.out0 = z; p.out1 = h_det;
+    p.wp = f16 ? (const float*)L.wp2 : (const float*)L.wp3; p.bias = L.bias;
+    p.rng_err = f16 ? c->rng_err_dev : nullptr;
+    for (int t = 0; t < MAXTAPS; ++t) { p.tap_dh[t] = t / 3 - 1; p.tap_dw[t] = t % 3 - 1; }     // cross-correlation, SAME
+    const int tm = 32;                                                                             // ppw 2, pxt 1
+    p.halo_before = W + 1;
+    p.nslot = tm + 2 * (W + 1);
+    p.cin = L.cin; p.cout = L.cout; p.nchunk = L.nchunk; p.ncot = L.ncot; p.cp = L.cin + 8;
+    int rc = raise_lds_cap((const void*)fn, lds);
+    if (rc) return rc;
+    dim3 grid((p.P + tm - 1) / tm, (p.pr_nlt + nt * wco - 1) / (nt * wco));
+    p.gx = (int)grid.x;
+    p.lds_bytes = (int)lds;
+    hipLaunchKernelGGL(fn, grid, dim3(64 * 4 * wco), lds, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
 }
 
 // ---- the downsampling IAFLayer's two strided convs at their minimal work (iaf_conv_bf3.hpp, template parameter S2) ------------

@@ -24,7 +24,9 @@
 //   K loop       steps (pair, tap) with a register ring of RD+1 step slots; refills are clamped to the wave's last step
 //                so every body is branch-free straight-line code (counted s_waitcnt).
 // Epilogues: the same fused epilogues as the fp32 kernel (bias + context + ELU -> pixel-major scratch; output pair ->
-// affine transform + log-det term / posterior KL elements), shared code in iaf_conv_epilogue.hpp.
+// affine transform + log-det term / posterior KL elements), shared code in iaf_conv_epilogue.hpp.  EPI_PRIOR: down_conv1 in prior form
+// (mode "sample", tf_train.py:52-54,56,60-61) -- the launched co tiles map onto the pz_mean / pz_logsd / h_det tiles of the conv's own pack
+// (prior_pack_tile: the other half of the pack is never read), paired (mean, logsd) like EPI_OUT's units, z = mean + exp(logsd) eps stored.
 #pragma once
 #include "iaf_conv_epilogue.hpp"
 
@@ -134,6 +136,7 @@ __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP
         asm volatile("" ::"s"(p.tap_dh[5]), "s"(p.tap_dh[6]), "s"(p.tap_dh[7]), "s"(p.tap_dh[8]), "s"(p.tap_dw[5]), "s"(p.tap_dw[6]),
                      "s"(p.tap_dw[7]), "s"(p.tap_dw[8]));
     if constexpr (EPI == EPI_PLAIN) asm volatile("" ::"s"(p.x2), "s"(p.res), "s"(p.c_split), "s"(p.in_elu), "s"(p.nsplit));
+    if constexpr (EPI == EPI_PRIOR) asm volatile("" ::"s"(p.in_elu), "s"(p.eps), "s"(p.pr_nzt), "s"(p.pr_nht), "s"(p.pr_nlt));
     if constexpr (EPI == EPI_DGRAD) asm volatile("" ::"s"(p.res), "s"(p.nsplit), "s"(p.qm), "s"(p.ql));
     asm volatile("" ::"s"(p.bias), "s"(p.ctx), "s"(p.ctx2), "s"(p.y), "s"(p.zin), "s"(p.out0), "s"(p.out1), "s"(p.border));
     if constexpr (INMODE == IN_POSTERIOR || EPI == EPI_OUT)
@@ -197,6 +200,7 @@ __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP
     // CU at NT = 2 and the weight stream bound the launch; on the fp16 planes the searched shapes are 512-thread workgroups, one per CU, and the
     // staging is exposed (round 6: tail_fold below, profiles/r06/experiments/ab_plain_conv_tail_slots_same_box.txt).
     constexpr int NWV = NTHREADS / 64;
+    constexpr bool PLAIN_IN = EPI == EPI_PLAIN || EPI == EPI_PRIOR;   // [elu](x) staged (EPI_PRIOR: down_conv1's input, no concat)
     constexpr int SQ = 10;                                         // quads in flight per thread (c_in <= 40 NWV: every c_in the packs allow at 8 waves)
     f32x4 nb_v[SQ];
     int nb_slot = -1, nb_q0 = 0, nb_nq = 0;
@@ -231,7 +235,7 @@ __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP
             const int q = nb_q0 + u * NWV;
             if (q >= nq) continue;
             f32x4 v = nb_v[u];
-            if (EPI == EPI_PLAIN && p.in_elu) {
+            if (PLAIN_IN && p.in_elu) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = elu_f(v[r]);
             }
@@ -268,7 +272,7 @@ __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP
     };
     auto tail_finish = [&]() __attribute__((always_inline)) {
         f32x4 v = tl_v;
-        if (EPI == EPI_PLAIN && p.in_elu) {
+        if (PLAIN_IN && p.in_elu) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = elu_f(v[r]);
         }
@@ -285,15 +289,17 @@ __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP
     const int S = S2 == 2 ? npair << lgt : npair * NTP;
     const int s0 = (kh * S) / KS, s1 = ((kh + 1) * S) / KS;
     const size_t wstep = (size_t)p.ncot * NPL * 64;                             // f32x4 per step
-    const f32x4* wbase = (const f32x4*)p.wp + (size_t)cot0 * NPL * 64 + lane;  // this wave's tiles, this lane's 16 bytes
+    // EPI_PRIOR: launched tiles are not pack tiles (prior_pack_tile): offsets from the pack's first tile
+    const int tbase = EPI == EPI_PRIOR ? 0 : cot0;
+    const f32x4* wbase = (const f32x4*)p.wp + (size_t)tbase * NPL * 64 + lane;  // this wave's tiles, this lane's 16 bytes
     // ragged co groups (round 6: c_out / 16 need not be a multiple of NT x WCO -- down_conv1's 28 tiles in three workgroups of 2 x 5 per
     // pixel block instead of seven of 2 x 2): a tile past the layer's last one reads the last one's fragments (a valid address; its
     // sums are computed and dropped -- the epilogue's items of such tiles are inactive)
     int toff[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        const int ta = cot0 + t < p.ncot ? cot0 + t : p.ncot - 1;
-        toff[t] = (ta - cot0) * NPL * 64;
+        const int ta = EPI == EPI_PRIOR ? prior_pack_tile(p, cot0 + t) : (cot0 + t < p.ncot ? cot0 + t : p.ncot - 1);
+        toff[t] = (ta - tbase) * NPL * 64;
     }
     f32x4 wr[U][NT][NPL];
     // fragments [lo, hi) of step s -> ring slot I (a step's refill is issued in PPW parts, one per pixel-tile group of
@@ -730,7 +736,7 @@ __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP
     IAF_BSTAMP(3);
     // ================= split-K exchange through LDS + epilogue ========================================================
     // item = (pixel tile q of this wave group, epilogue unit u); the KS waves of a group share the items round-robin
-    constexpr bool ONE_TILE_UNITS = (EPI != EPI_OUT);
+    constexpr bool ONE_TILE_UNITS = (EPI != EPI_OUT && EPI != EPI_PRIOR);   // EPI_PRIOR: (pz_mean, pz_logsd) or (h_det, h_det) pairs
     constexpr int TPU = ONE_TILE_UNITS ? 1 : 2;
     constexpr int NUNIT = NT / TPU;
     constexpr int NITEM = PPW * NUNIT;
@@ -741,7 +747,7 @@ __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP
     for (int i = 0; i < NMY; ++i) {
         const int item = kh + i * KS;
         const int q = item / NUNIT, u = item - q * NUNIT;
-        g[i] = epi_geom(p, P0 + (pw * PPW + q) * 16 + pl, kk, item < NITEM && cot0 + u * TPU < p.ncot);
+        g[i] = epi_geom(p, P0 + (pw * PPW + q) * 16 + pl, kk, item < NITEM && cot0 + u * TPU < (EPI == EPI_PRIOR ? p.pr_nlt : p.ncot));
         if constexpr (S2 == 2) g[i].up = 4 + 2 * ph_a + ph_b;
         epi_load<EPI>(p, g[i], cot0 + u * TPU, ops[i]);
     }

@@ -1,6 +1,7 @@
 // iaf_conv_bf3_plain_inst.hip -- instantiates iaf_conv_bf3_kernel with all 9 taps for the plain weight-normed conv2d around
 // the IAF step (up_conv1/3, down_conv1/2, tf_train.py:36,41,53,93): NCHW input with the graph's elu / concat, EPI_PLAIN
-// epilogue (bias, split store, residual), ONE launch shape per translation unit.  Built by iaf_amd/build.py.
+// epilogue (bias, split store, residual), and down_conv1 in prior form (EPI_PRIOR), ONE launch shape per translation unit.
+// Built by iaf_amd/build.py.
 #include "iaf_conv_bf3.hpp"
 
 #ifndef IAF_WCO
@@ -79,6 +80,23 @@ extern "C" conv_fn_t IAF_CAT(iaf_pick_bf3p16d_, IAF_PPW, IAF_PXT, IAF_KS, IAF_WC
 #if IAF_WCO < 3
         case 5: return iaf_conv_bf3_kernel<5, IAF_PPW, IAF_PXT, IAF_KS, IN_PIXMAJOR, EPI_DGRAD, IAF_WCO, MAXTAPS, 0, 1>;
 #endif
+    }
+    return nullptr;
+}
+
+// down_conv1 in prior form (iaf_conv_bf3.hpp, EPI_PRIOR; iaf_conv3x3_forward_prior_sample): two-tile units, so NT = 2 or 4;
+// f16 = 1 the two fp16 planes (p.wp = the two-plane pack), 0 the bf16x3 planes
+extern "C" conv_fn_t IAF_CAT(iaf_pick_bf3pz_, IAF_PPW, IAF_PXT, IAF_KS, IAF_WCO)(int nt, int f16) {
+    if (f16) {
+        switch (nt) {
+            case 2: return iaf_conv_bf3_kernel<2, IAF_PPW, IAF_PXT, IAF_KS, IN_NCHW, EPI_PRIOR, IAF_WCO, MAXTAPS, 0, 1>;
+            case 4: return iaf_conv_bf3_kernel<4, IAF_PPW, IAF_PXT, IAF_KS, IN_NCHW, EPI_PRIOR, IAF_WCO, MAXTAPS, 0, 1>;
+        }
+        return nullptr;
+    }
+    switch (nt) {
+        case 2: return iaf_conv_bf3_kernel<2, IAF_PPW, IAF_PXT, IAF_KS, IN_NCHW, EPI_PRIOR, IAF_WCO, MAXTAPS>;
+        case 4: return iaf_conv_bf3_kernel<4, IAF_PPW, IAF_PXT, IAF_KS, IN_NCHW, EPI_PRIOR, IAF_WCO, MAXTAPS>;
     }
     return nullptr;
 }

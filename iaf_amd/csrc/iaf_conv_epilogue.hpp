@@ -46,6 +46,18 @@ __device__ __forceinline__ EpiGeom epi_geom(const ConvP& p, int Pl, int kk, bool
     return g;
 }
 
+// EPI_PRIOR (down_conv1 in prior form): launched tile lt -> the tile of down_conv1's pack it multiplies.  Two-tile units: u < nzt pairs
+// pz_mean tile u (pack tile u) with pz_logsd tile u (nzt + u); the units behind them pair h_det tiles 2j, 2j+1 (pack 4 nzt + nht + ...).
+// Tiles past the launch (ragged co groups) and the missing partner of an odd h_det count read a valid tile; their sums are dropped.
+__device__ __forceinline__ int prior_pack_tile(const ConvP& p, int lt) {
+    lt = lt < p.pr_nlt ? lt : p.pr_nlt - 1;
+    const int u = lt >> 1, e = lt & 1;
+    if (u < p.pr_nzt) return e ? p.pr_nzt + u : u;
+    int j = 2 * (u - p.pr_nzt) + e;
+    j = j < p.pr_nht ? j : p.pr_nht - 1;
+    return 4 * p.pr_nzt + p.pr_nht + j;
+}
+
 // operands of the epilogue that do not depend on the GEMM (issued before the split-K exchange so their latency hides)
 template <int EPI>
 __device__ __forceinline__ void epi_load(const ConvP& p, const EpiGeom& g, int cot, EpiOps& o) {
@@ -83,6 +95,15 @@ __device__ __forceinline__ void epi_load(const ConvP& p, const EpiGeom& g, int c
         } else {                                                                          // MODE_DGRAD_Z: dz_new, logsd (NCHW)
 #pragma unroll
             for (int r = 0; r < 4; ++r) { o.pre0[r] = p.qm[cb + (size_t)r * HW]; o.pre1[r] = p.ql[cb + (size_t)r * HW]; }
+        }
+    } else if (EPI == EPI_PRIOR) {  // cot = the unit's first launched tile: biases of both pack tiles; a z unit's noise
+        const int u = cot >> 1;
+        o.b0 = *(const f32x4*)(p.bias + prior_pack_tile(p, cot) * 16 + 4 * g.kk);
+        o.b1 = *(const f32x4*)(p.bias + prior_pack_tile(p, cot + 1) * 16 + 4 * g.kk);
+        if (u < p.pr_nzt) {
+            const size_t zb = ((size_t)g.bimg * (p.pr_nzt * 16) + u * 16 + 4 * g.kk) * HW + g.pp;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o.pre0[r] = p.eps[zb + (size_t)r * HW];
         }
     } else {
         o.b0 = *(const f32x4*)(p.bias + cot * 16 + 4 * g.kk);
@@ -164,6 +185,26 @@ __device__ __forceinline__ void epi_apply(const ConvP& p, const EpiGeom& g, int 
             const size_t cb = ((size_t)g.bimg * p.cout + co) * HW + g.pp;
 #pragma unroll
             for (int r = 0; r < 4; ++r) p.out0[cb + (size_t)r * HW] = v[r] + o.pre0[r] * __expf(-o.pre1[r]);
+        }
+    } else if (EPI == EPI_PRIOR) {
+        const int u = cot >> 1;
+        if (u < p.pr_nzt) {         // z = DiagonalGaussian(pz_mean, 2 pz_logsd).sample (tf_train.py:56,61): iaf_gauss_sample_kernel's expression
+            const size_t zb = ((size_t)g.bimg * (p.pr_nzt * 16) + u * 16 + 4 * g.kk) * HW + g.pp;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float m = v0[r] + o.b0[r], s = v1[r] + o.b1[r];
+                p.out0[zb + (size_t)r * HW] = m + expf(0.5f * (2.0f * s)) * o.pre0[r];
+            }
+        } else {                    // h_det (tf_train.py:54), both tiles of the unit (the second only if n_h has it)
+            const int j = 2 * (u - p.pr_nzt);
+            const size_t hb = ((size_t)g.bimg * (p.pr_nht * 16) + j * 16 + 4 * g.kk) * HW + g.pp;
+            const f32x4 h0 = v0 + o.b0, h1 = v1 + o.b1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p.out1[hb + (size_t)r * HW] = h0[r];
+            if (j + 1 < p.pr_nht) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) p.out1[hb + (size_t)(16 + r) * HW] = h1[r];
+            }
         }
     } else {
         const int nz = p.cout >> 1;

@@ -31,6 +31,8 @@ __device__ __forceinline__ void static_for(F&& f) {
 #define EPI_DGRAD9 5   // host-side selector only: EPI_DGRAD with all 9 taps (data gradient of a plain conv)
 #define EPI_HIDDEN_DEEP 6   // host-side selector only: EPI_HIDDEN, pixel-major input, double-depth weight ring
 #define EPI_PLAIN 3    // y = acc + bias [-> res + 0.1*y]  -> NCHW   (plain weight-normed conv2d, layers.py:63-64; tf_train.py:44,94)
+#define EPI_PRIOR 7    // down_conv1 in prior form (mode "sample", tf_train.py:52-54,56,60-61): only the pz_mean / pz_logsd / h_det tiles;
+                       // z = pz_mean + exp(pz_logsd) eps and h_det + bias -> NCHW (iaf_conv_bf3.hpp, iaf_conv_epilogue.hpp)
 
 #define MODE_RAW 0        // out0 = m_raw, out1 = s_raw                         (layers.py:166)
 #define MODE_IAF 1        // out0 = (z-0.1m)/exp(0.1s), out1 = 0.1s             (tf_train.py:70-72)
@@ -101,6 +103,9 @@ struct ConvP {
     const unsigned* inv_done;
     // two-plane fp16 kernels (iaf_conv_bf3.hpp F16): host-visible word raised when an operand beyond fp16's largest finite number was staged
     unsigned* rng_err;
+    // EPI_PRIOR: 16-channel tiles of n_z (pr_nzt) and of n_h (pr_nht); launched tiles pr_nlt = 2 pr_nzt + 2 ceil(pr_nht / 2), in two-tile units
+    // (pz_mean tile u, pz_logsd tile u) for u < pr_nzt, then (h_det tile 2j, 2j+1).  eps / out0 = z [B,n_z,H,W], out1 = h_det [B,n_h,H,W]
+    int pr_nzt, pr_nht, pr_nlt;
 };
 
 // Pin the order "MFMAs with memory instructions spread evenly between them" inside the current scheduling region:

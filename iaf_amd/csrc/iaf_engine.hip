@@ -331,6 +331,18 @@ static conv_fn_t pick_bf3_plain_f16(int nt, int ppw, int pxt, int ks, int wco) {
     if (ppw == 2 && pxt == 1 && ks == 4 && wco == 3) return iaf_pick_bf3p16_2_1_4_3(nt);
     return nullptr;
 }
+extern "C" conv_fn_t iaf_pick_bf3pz_2_1_4_1(int nt, int f16);
+extern "C" conv_fn_t iaf_pick_bf3pz_4_1_4_1(int nt, int f16);
+extern "C" conv_fn_t iaf_pick_bf3pz_2_1_4_2(int nt, int f16);
+extern "C" conv_fn_t iaf_pick_bf3pz_2_1_4_3(int nt, int f16);
+// ... down_conv1 in prior form (EPI_PRIOR, iaf_conv3x3_forward_prior_sample), on bf16 (f16 = 0) or two fp16 planes (f16 = 1)
+static conv_fn_t pick_bf3_prior(int nt, int ppw, int pxt, int ks, int wco, int f16) {
+    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3pz_2_1_4_1(nt, f16);
+    if (ppw == 4 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3pz_4_1_4_1(nt, f16);
+    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 2) return iaf_pick_bf3pz_2_1_4_2(nt, f16);
+    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 3) return iaf_pick_bf3pz_2_1_4_3(nt, f16);
+    return nullptr;
+}
 // LDS of a 9-tap bf16x3 launch: the pixel tile with a halo of W + 1 slots on BOTH sides (+ the zero slot)
 static size_t bf3_plain_lds_bytes(int cin, int W, int nt, int ppw, int pxt, int ks, int wco, int npl = 3) {
     const size_t tile = (size_t)(16 * ppw * pxt + 2 * (W + 1) + 1) * (npl * (cin / 8) + 2) * 16;

@@ -8,7 +8,7 @@ import ctypes
 import torch
 
 from . import _capi
-from .layers import ARStack, WNConv2d, resample2, _ptr, _stream
+from .layers import ARStack, WNConv2d, resample2, _check_act, _ptr, _stream
 
 
 class IAFPosterior(object):
@@ -134,6 +134,11 @@ class IAFLayer(object):
     def down(self, inp, eps, autotune=False, eps_prior=None):
         return self._range_retry(self._down, inp, eps, autotune, eps_prior)
 
+    def generate_down(self, inp, eps_prior):
+        """down() of mode "sample" (tf_train.py:46-66, 87-95) without the up pass: z = the prior sample, no IAF step, no KL.  inp
+        [B,h_size,H,W], eps_prior [B,z_size,H,W]; returns the output (a downsampling layer's at 2H x 2W).  Needs only load()."""
+        return self._range_retry(self._generate_down, inp, eps_prior)
+
     def up_train(self, inp, autotune=False):
         return self._range_retry(self._up_train, inp, autotune)
 
@@ -189,6 +194,23 @@ class IAFLayer(object):
             out = self.down_conv2(blk["z"], x2=h_det, elu_input=True, residual=inp, autotune=autotune)[0]  # :87-94
         self.last_block = blk
         return out, blk["kl_obj"], blk["kl_cost"]
+
+    def _generate_down(self, inp, eps_prior):
+        zs, hs = self.z_size, self.h_size
+        _check_act(inp, "inp")
+        B, _, H, W = (int(v) for v in inp.shape)
+        _check_act(eps_prior, "eps_prior", (B, zs, H, W))
+        rc, z, h_det = self.down_conv1._prior_sample(inp, eps_prior, zs, elu_input=True)                # :52-54,56,60-61
+        if rc in (_capi.IAF_ERR_UNSUPPORTED, _capi.IAF_ERR_NOT_PREPARED):
+            # no fused form for this conv (channels not multiples of 16, fp32 pinned), or trim_packs kept only the fp32 pack: the full
+            # down_conv1 and the prior sample in a launch of its own (an unprepared conv says so here)
+            pz_mean, pz_logsd, _, _, _, h_det = self.down_conv1(inp, elu_input=True, split=[zs] * 4 + [hs] * 2)
+            z = gaussian_sample(pz_mean, pz_logsd, eps_prior)
+        else:
+            _capi.check(rc)
+        if self.downsample:                                                                               # :87-91, 94
+            return self.down_conv2.deconv(z, x2=h_det, elu_input=True, residual=inp)
+        return self.down_conv2(z, x2=h_det, elu_input=True, residual=inp)[0]
 
     # -- training: forward that keeps what the backward needs, and the backward (tf_train.py:138 for this layer) -----
     def set_training(self, on=True):

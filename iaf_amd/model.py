@@ -253,6 +253,50 @@ class CVAE1(object):
         xf = self._bottom_up(x, noise)
         return self._top_down(xf, int(x.shape[0]), noise, terms=_terms)
 
+    def generate(self, eps_prior):
+        """Images from the prior: the reference's m_trunc[0] of CVAE1(hps, "sample") with no image fed (tf_train.py:300, 358-362) -- TF runs
+        only the top-down pass: the tiled h_top (:189-192), every layer's down() in mode "sample" (IAFLayer.generate_down: down_conv1 in
+        prior form, no IAF step, no KL), x_dec + clip (:206-208).  eps_prior: per layer in top-down order the prior noise, i.e. the
+        eps_prior half of forward()'s noise list, fp32 device tensors [B,z_size,S_l,S_l]; B comes from them (k is not applied).
+        Returns x_out [B,3,S,S].  Works whatever `mode` the model was built with (the variables are the same); after load(params).
+        No host synchronisation: capturable with torch.cuda.graph."""
+        B = self._check_prior_noise(eps_prior)
+        lib, p, hs, S = _capi.lib(), self.params, self.h_size, self.image_size
+        dev = eps_prior[0].device
+        St = S // 2 ** self.depth
+        h = torch.empty((B, hs, St, St), dtype=torch.float32, device=dev)
+        _capi.check(lib.iaf_tile_channels(_ptr(p["h_top"]), _ptr(h), B, hs, St * St, _stream()))          # :189-192
+        li = 0
+        for level in reversed(self.layers):                                                                # :195-200
+            for layer in reversed(level):
+                h = layer.generate_down(h, eps_prior[li])
+                li += 1
+        x_out = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+        _capi.check(lib.iaf_deconvk_forward(_ptr(h), _ptr(self._w_dec), _ptr(p["x_dec/b"]), _ptr(x_out), B, hs, S // 2, S // 2, 3, 5, 5,
+                                            2, 1, -0.5 + 1 / 512., 0.5 - 1 / 512., _stream()))             # :206-208
+        return x_out
+
+    def _check_prior_noise(self, eps_prior):
+        """what generate() requires of its noise list (host-only checks, before any launch); returns B"""
+        if self.params is None:
+            raise RuntimeError("CVAE1.load(params) first")
+        nl = self.depth * self.num_blocks
+        if not isinstance(eps_prior, (list, tuple)) or len(eps_prior) != nl:
+            raise ValueError("eps_prior: %d tensors expected (the prior noise of every layer, top-down)" % nl)
+        e0 = eps_prior[0]
+        if not torch.is_tensor(e0) or e0.dim() != 4 or int(e0.shape[0]) < 1:
+            raise ValueError("eps_prior[0]: a [B,%d,S_l,S_l] tensor" % self.z_size)
+        B, li = int(e0.shape[0]), 0
+        for i in reversed(range(self.depth)):
+            Sl = self.image_size // 2 ** (i + 1)
+            for _ in range(self.num_blocks):
+                e = eps_prior[li]
+                if (not torch.is_tensor(e) or e.dtype != torch.float32 or not e.is_cuda or not e.is_contiguous() or e.device != e0.device
+                        or tuple(e.shape) != (B, self.z_size, Sl, Sl)):
+                    raise ValueError("eps_prior[%d]: a contiguous fp32 device tensor [%d,%d,%d,%d]" % (li, B, self.z_size, Sl, Sl))
+                li += 1
+        return B
+
     def _bottom_up(self, x, noise):
         """tf_train.py:153-187: image scaling (+ repeat k), x_enc, the up pass of every layer (which leaves qz_mean, qz_logsd, up_context in
         the layers, :38).  Returns the scaled image the likelihood compares with."""

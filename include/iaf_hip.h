@@ -596,6 +596,18 @@ int iaf_conv3x3_forward_stride2(iaf_conv3x3_t* c, const float* x, int elu_input,
                                 int n_outs, int B, int H, int W, void* stream);
 int iaf_conv3x3_forward_deconv(iaf_conv3x3_t* c, const float* x, const float* x2, int c_split, int elu_input,
                                const float* residual, float* out, int B, int H, int W, void* stream);
+/* down_conv1 of an IAFLayer in mode "sample", fused with the prior sample (tf_train.py:52-54 the conv and its split, :56 the prior
+ * DiagonalGaussian(pz_mean, 2 pz_logsd), :60-61 its sample):  [pz_mean, pz_logsd, ., ., ., h_det] = conv2d([elu](x)) split
+ * [n_z x 4, n_h x 2];  z = pz_mean + exp(pz_logsd) * eps (iaf_gaussian_sample_logsd's expression);  h_det as it is.  Only the output
+ * channels sample mode reads are computed ((2 n_z + n_h) of 4 n_z + 2 n_h), read from the conv's own pack; pz_mean / pz_logsd are never
+ * stored.  c: a prepared plain conv with n_out = 4 n_z + 2 n_h.  x [B,n_in,H,W]; eps, z [B,n_z,H,W]; h_det [B,n_h,H,W].
+ * Arithmetic: two fp16 planes where iaf_conv3x3_forward at this (B, H, W) runs them (iaf_conv3x3_runs_f16x2; the same range word:
+ * IAF_ERR_RANGE once on the next call, then bf16 planes), else the bf16x3 planes (also below the forward's size rule).
+ * Errors: IAF_ERR_NULL / IAF_ERR_SHAPE (n_out != 4 n_z + 2 n_h) before any device work; IAF_ERR_UNSUPPORTED where no fused form exists
+ * (n_z or n_h not a multiple of 16, generic channel counts, masked convs, deconvs, IAF_PRECISION_F32): the caller then runs
+ * iaf_conv3x3_forward + iaf_gaussian_sample_logsd; IAF_ERR_NOT_PREPARED as iaf_conv3x3_forward (incl. a pack iaf_conv3x3_set_packs dropped). */
+int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, const float* eps, float* z,
+                                     float* h_det, int B, int H, int W, void* stream);
 /* eps_out with (qz_mean+rz_mean) + exp(qz_logsd+rz_logsd)*eps_out == z: mode "init" of IAFLayer.down runs the posterior
  * block on a PRIOR sample (tf_train.py:60-61, 67-85) */
 int iaf_noise_from_sample(const float* z, const float* qz_mean, const float* qz_logsd, const float* rz_mean,
