@@ -1,10 +1,12 @@
 """Build the HIP engine in-tree for gfx950:  python -m iaf_amd.build [--force]
 Output: iaf_amd/_lib/libiaf_hip.so (git-ignored; travels to the GPU box with the snapshot).
 
-The masked-conv kernel is instantiated once per launch shape (pxt, wco, ks) in its own translation
-unit (csrc/iaf_conv_inst.hip with -DIAF_PXT/-DIAF_WCO/-DIAF_KS); the units compile in parallel."""
+The conv kernels are instantiated once per launch shape, and the one-launch step once per part, each in its own translation
+unit (e.g. csrc/iaf_conv_inst.hip with -DIAF_PXT/-DIAF_WCO/-DIAF_KS); the units compile in parallel.  Which shapes and parts
+exist is csrc/iaf_variants.def, read here and included by the engine."""
 import concurrent.futures
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -18,9 +20,30 @@ _TAG = os.environ.get("IAF_BUILD_TAG", "")
 LIBDIR = os.path.join(HERE, "_lib" + ("_" + _TAG if _TAG else ""))
 OBJDIR = os.path.join(LIBDIR, "obj")
 OUT = os.path.join(LIBDIR, "libiaf_hip.so")
-SHAPES = [(4, 1, 1), (4, 1, 2), (2, 2, 1), (2, 2, 2), (2, 1, 2), (2, 1, 4), (1, 1, 4), (1, 2, 2)]   # keep in sync with pick_kernel()
-BF3_PLAIN_SHAPES = [(2, 1, 4, 1), (4, 1, 4, 1), (2, 1, 4, 2), (2, 1, 4, 3)]   # 9-tap plain convs: keep in sync with pick_bf3_plain()
-BF3_SHAPES = [(4, 1, 4, 1), (2, 1, 4, 1), (1, 1, 4, 1), (1, 4, 1, 1), (2, 1, 4, 2), (1, 1, 4, 2)]   # (ppw, pxt, ks, wco): keep in sync with pick_bf3()
+VARIANTS = os.path.join(CSRC, "iaf_variants.def")
+
+
+def _read_variants(path=VARIANTS):
+    """{macro: [argument tuple, ...]} in file order; any line that is not a comment, an entry or the file's own macro plumbing is an error"""
+    arity = {"IAF_CONV": 3, "IAF_BF3": 4, "IAF_BF3P": 5, "IAF_STEP_PART": 1}
+    out = {k: [] for k in arity}
+    for n, line in enumerate(open(path), 1):
+        line = line.strip()
+        if not line or line.startswith("//") or re.fullmatch(r"#(ifndef|undef) IAF_\w+|#define IAF_\w+\([\w, ]*\)|#endif", line):
+            continue
+        m = re.fullmatch(r"(IAF_\w+)\(([\d, ]*)\)", line)
+        args = tuple(int(a) for a in m.group(2).split(",")) if m else ()
+        if not m or len(args) != arity.get(m.group(1), -1):
+            raise ValueError("%s:%d: not a variant entry: %r" % (path, n, line))
+        out[m.group(1)].append(args)
+    return out
+
+
+_V = _read_variants()
+SHAPES = _V["IAF_CONV"]                # exact-fp32 conv: (pxt, wco, ks)
+BF3_SHAPES = _V["IAF_BF3"]             # bf16x3 masked conv: (ppw, pxt, ks, wco)
+BF3_PLAIN_SHAPES = _V["IAF_BF3P"]      # 9-tap plain conv: (ppw, pxt, ks, wco, strided / deconv forms compiled)
+STEP_PARTS = [p for (p,) in _V["IAF_STEP_PART"]]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 CFLAGS += os.environ.get("IAF_EXTRA_CFLAGS", "").split()       # dev experiments only (e.g. -DIAF_EXP_NOREFILL)
 HEADERS = [os.path.join(ROOT, "include", "iaf_hip.h")] + sorted(
@@ -39,12 +62,12 @@ def _units():
     for ppw, pxt, ks, wco in BF3_SHAPES:
         units.append((os.path.join(CSRC, "iaf_conv_bf3_inst.hip"), os.path.join(OBJDIR, "iaf_bf3_%d_%d_%d_%d.o" % (ppw, pxt, ks, wco)),
                       ["-DIAF_PPW=%d" % ppw, "-DIAF_PXT=%d" % pxt, "-DIAF_KS=%d" % ks, "-DIAF_WCO=%d" % wco]))
-    for ppw, pxt, ks, wco in BF3_PLAIN_SHAPES:
+    for ppw, pxt, ks, wco, s2 in BF3_PLAIN_SHAPES:
         units.append((os.path.join(CSRC, "iaf_conv_bf3_plain_inst.hip"), os.path.join(OBJDIR, "iaf_bf3p_%d_%d_%d_%d.o" % (ppw, pxt, ks, wco)),
-                      ["-DIAF_PPW=%d" % ppw, "-DIAF_PXT=%d" % pxt, "-DIAF_KS=%d" % ks, "-DIAF_WCO=%d" % wco]))
+                      ["-DIAF_PPW=%d" % ppw, "-DIAF_PXT=%d" % pxt, "-DIAF_KS=%d" % ks, "-DIAF_WCO=%d" % wco, "-DIAF_S2=%d" % s2]))
     # accumulators in architectural VGPRs: left to itself the register allocator puts them in AGPRs and rotates them through
     # VGPR copies inside the K loop (48 v_accvgpr moves per 162 MFMAs)
-    for part in (0, 1, 2, 3, 4, 5, 6):
+    for part in STEP_PARTS:
         units.append((os.path.join(CSRC, "iaf_step_fused_inst.hip"), os.path.join(OBJDIR, "iaf_step_fused_%d.o" % part),
                       ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-DIAF_FUSED_PART=%d" % part]))
     return units
@@ -61,10 +84,10 @@ def _deps(obj, src):
     """headers the unit actually includes (hipcc -MD wrote obj + '.d' at the last compile), else every project header"""
     d = obj + ".d"
     if not os.path.exists(d):
-        return [src] + HEADERS
+        return [src, VARIANTS] + HEADERS
     words = open(d).read().replace("\\\n", " ").split()
     mine = [w for w in words[1:] if w.startswith(ROOT) or not os.path.isabs(w)]      # project files only (not /opt/rocm)
-    return [src] + mine
+    return [src, VARIANTS] + mine          # (the variant list also sets units' -D flags)
 
 
 def build(force=False, verbose=True, jobs=None):

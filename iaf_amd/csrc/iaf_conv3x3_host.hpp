@@ -367,7 +367,7 @@ extern "C" int iaf_conv3x3_set_tuning(iaf_conv3x3_t* c, int nt, int pxt, int wco
     GemmLayer& L = c->L;
     if (nt == 0) { L.user_tuned = false; c->bf3_choice = 1; return IAF_OK; }     // back to the automatic choice
     if (nt < 0) {           // a bf16x3 launch shape, as iaf_conv3x3_autotune reports it: (-nt, ppw, wco, ks), pxt = 1
-        if (c->generic || c->mask_mode || !L.wp3 || !bf3_ragged_ok(L.ncot, -nt * wco) || !pick_bf3_plain(-nt, pxt, 1, ks, wco)) return IAF_ERR_UNSUPPORTED;
+        if (c->generic || c->mask_mode || !L.wp3 || !bf3_ragged_ok(L.ncot, -nt * wco) || !pick_bf3p(-nt, pxt, 1, ks, wco, BF3P_PLAIN)) return IAF_ERR_UNSUPPORTED;
         L.b_nt = -nt; L.b_ppw = pxt; L.b_pxt = 1; L.b_ks = ks; L.b_wco = wco;
         c->bf3_choice = 2;
         return IAF_OK;
@@ -397,7 +397,7 @@ static bool conv3x3_bf3_shape(GemmLayer& L, int choice, long long P, int W, bool
         for (int i = 0; i < 8; ++i) {
             const int nt = cand[i][0], wco = cand[i][1], per = nt * wco;
             const int covered = (L.ncot + per - 1) / per * per;
-            if ((covered - L.ncot) * 8 > L.ncot || !pick_bf3_plain(nt, 2, 1, 4, wco)) continue;
+            if ((covered - L.ncot) * 8 > L.ncot || !pick_bf3p(nt, 2, 1, 4, wco, BF3P_PLAIN)) continue;
             if (bf3_plain_lds_bytes(L.cin, W, nt, 2, 1, 4, wco, f16 ? 2 : 3) > 160 * 1024) continue;
             const long long wgs = nblk * (covered / per);
             if (wgs >= 256) { best = i; break; }
@@ -406,7 +406,7 @@ static bool conv3x3_bf3_shape(GemmLayer& L, int choice, long long P, int W, bool
         if (best < 0) return false;
         L.b_nt = cand[best][0]; L.b_ppw = 2; L.b_pxt = 1; L.b_ks = 4; L.b_wco = cand[best][1];
     }
-    if (!bf3_ragged_ok(L.ncot, L.b_nt * L.b_wco) || !pick_bf3_plain(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco)) return false;
+    if (!bf3_ragged_ok(L.ncot, L.b_nt * L.b_wco) || !pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, BF3P_PLAIN)) return false;
     return bf3_plain_lds_bytes(L.cin, W, L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, f16 ? 2 : 3) <= 160 * 1024;
 }
 
@@ -423,15 +423,15 @@ static int conv3x3_launch(GemmLayer& L, ConvP& p, int epi_sel, int inmode, bool 
     const bool bwd3 = !masked && mirror && epi_sel == EPI_DGRAD9 && inmode == IN_PIXMAJOR && variant == IAF_VARIANT_TF;
     const bool f16l = (fwd3 && f16_rng != nullptr) || (bwd3 && dgrad16 && L.wp2 != nullptr);
     if ((fwd3 || bwd3) && conv3x3_bf3_shape(L, bf3_choice, p.P, p.W, f16l) &&
-        pick_bf3_plain(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, bwd3 ? EPI_DGRAD : EPI_PLAIN)) {
-        conv_fn_t fn = pick_bf3_plain(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, bwd3 ? EPI_DGRAD : EPI_PLAIN);
+        pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, bwd3 ? BF3P_DGRAD : BF3P_PLAIN)) {
+        conv_fn_t fn = pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, bwd3 ? BF3P_DGRAD : BF3P_PLAIN);
         const int tm = 16 * L.b_ppw * L.b_pxt, W = p.W, sg = bwd3 ? -1 : 1;
         p.border = nullptr; p.wp = (const float*)L.wp3; p.bias = L.bias; p.lim = nullptr;
         // f16_rng (the caller's conv runs IAF_PRECISION_F16X2): the forward on two fp16 planes, the same launch shape and LDS bound
         bool npl2 = false;
-        if (conv_fn_t fn16 = (fwd3 && f16_rng && L.wp2) ? pick_bf3_plain_f16(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco) : nullptr) {
+        if (conv_fn_t fn16 = (fwd3 && f16_rng && L.wp2) ? pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, BF3P_F16) : nullptr) {
             fn = fn16; p.wp = (const float*)L.wp2; p.rng_err = f16_rng; npl2 = true;
-        } else if (conv_fn_t fd16 = (bwd3 && dgrad16 && L.wp2) ? pick_bf3_plain_f16d(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco) : nullptr) {
+        } else if (conv_fn_t fd16 = (bwd3 && dgrad16 && L.wp2) ? pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, BF3P_F16_DGRAD) : nullptr) {
             fn = fd16; p.wp = (const float*)L.wp2; p.rng_err = nullptr; npl2 = true;
         } else if (f16l) {
             return IAF_ERR_UNSUPPORTED;         // (the shape was sized for two planes and no two-plane kernel exists for it: not reached by the compiled shape lists)
@@ -549,7 +549,7 @@ extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float
         // iaf_conv3x3_set_packs: the pack this launch reads must be one the prep launches write
         GemmLayer t = L;
         const bool split = conv_split(c) && !c->deconv && conv3x3_bf3_shape(t, c->bf3_choice, p.P, W, conv_f16_active(c));
-        const bool f16 = split && conv_f16_active(c) && pick_bf3_plain_f16(t.b_nt, t.b_ppw, t.b_pxt, t.b_ks, t.b_wco);
+        const bool f16 = split && conv_f16_active(c) && pick_bf3p(t.b_nt, t.b_ppw, t.b_pxt, t.b_ks, t.b_wco, BF3P_F16);
         const int need = f16 ? IAF_PACK_F16X2 : split ? IAF_PACK_BF16X3 : IAF_PACK_F32;
         if (!(c->packs & need)) return IAF_ERR_NOT_PREPARED;
     }
@@ -571,7 +571,7 @@ static conv_fn_t conv3x3_prior_shape(const GemmLayer& L, int nlt, long long P, i
     for (int i = 0; i < 6; ++i) {
         const int nt = cand[i][0], wco = cand[i][1], per = nt * wco;
         const int covered = (nlt + per - 1) / per * per;
-        if ((covered - nlt) * 8 > nlt || !pick_bf3_prior(nt, 2, 1, 4, wco, f16 ? 1 : 0)) continue;
+        if ((covered - nlt) * 8 > nlt || !pick_bf3p(nt, 2, 1, 4, wco, f16 ? BF3P_PRIOR_F16 : BF3P_PRIOR)) continue;
         if (bf3_plain_lds_bytes(L.cin, W, nt, 2, 1, 4, wco, f16 ? 2 : 3) > 160 * 1024) continue;
         const long long wgs = nblk * (covered / per);
         if (wgs >= 256) { best = i; break; }
@@ -580,7 +580,7 @@ static conv_fn_t conv3x3_prior_shape(const GemmLayer& L, int nlt, long long P, i
     if (best < 0) return nullptr;
     *nt_out = cand[best][0]; *wco_out = cand[best][1];
     *lds_out = bf3_plain_lds_bytes(L.cin, W, *nt_out, 2, 1, 4, *wco_out, f16 ? 2 : 3);
-    return pick_bf3_prior(*nt_out, 2, 1, 4, *wco_out, f16 ? 1 : 0);
+    return pick_bf3p(*nt_out, 2, 1, 4, *wco_out, f16 ? BF3P_PRIOR_F16 : BF3P_PRIOR);
 }
 
 extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, const float* eps, float* z,
@@ -622,15 +622,6 @@ extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x
 }
 
 // ---- the downsampling IAFLayer's two strided convs at their minimal work (iaf_conv_bf3.hpp, template parameter S2) ------------
-extern "C" conv_fn_t iaf_pick_bf3s_2_1_4_1(int nt, int s2);
-extern "C" conv_fn_t iaf_pick_bf3s_4_1_4_1(int nt, int s2);
-extern "C" conv_fn_t iaf_pick_bf3s_2_1_4_2(int nt, int s2);
-static conv_fn_t pick_bf3_s2(int nt, int ppw, int ks, int wco, int s2) {
-    if (ppw == 2 && ks == 4 && wco == 1) return iaf_pick_bf3s_2_1_4_1(nt, s2);
-    if (ppw == 4 && ks == 4 && wco == 1) return iaf_pick_bf3s_4_1_4_1(nt, s2);
-    if (ppw == 2 && ks == 4 && wco == 2) return iaf_pick_bf3s_2_1_4_2(nt, s2);
-    return nullptr;
-}
 // launch shape (nt, ppw, ks, wco; pxt = 1) of a strided conv: the first compiled one that divides the co tiles and fits LDS.
 // IAF_S2_SHAPE / IAF_DECONV_SHAPE="nt,ppw,ks,wco": dev override.
 static conv_fn_t s2_shape(const GemmLayer& L, int s2, int W, int* sh, size_t* lds_out) {
@@ -644,7 +635,7 @@ static conv_fn_t s2_shape(const GemmLayer& L, int s2, int W, int* sh, size_t* ld
         const int* q = i < 0 ? env : cand[s2 - 1][i];
         const int nt = q[0], ppw = q[1], ks = q[2], wco = q[3];
         if (nt <= 0 || wco <= 0 || L.ncot % (nt * wco) != 0) continue;
-        conv_fn_t fn = pick_bf3_s2(nt, ppw, ks, wco, s2);
+        conv_fn_t fn = pick_bf3p(nt, ppw, 1, ks, wco, s2 == 1 ? BF3P_S2 : BF3P_DECONV);
         if (!fn) continue;
         const int tm = 16 * ppw;
         const size_t slots = s2 == 1 ? (size_t)4 * tm + 2 * W + 2 + 1 : (size_t)tm + W + 1 + 1;
@@ -818,7 +809,7 @@ extern "C" int iaf_conv3x3_runs_f16x2(iaf_conv3x3_t* c, int B, int H, int W) {
     if (!iaf_conv3x3_runs_bf16x3(c, B, H, W) || !conv_f16_active(c)) return 0;
     GemmLayer t = c->L;
     if (!conv3x3_bf3_shape(t, c->bf3_choice, (long long)B * H * W, W, true)) return 0;
-    return pick_bf3_plain_f16(t.b_nt, t.b_ppw, t.b_pxt, t.b_ks, t.b_wco) ? 1 : 0;
+    return pick_bf3p(t.b_nt, t.b_ppw, t.b_pxt, t.b_ks, t.b_wco, BF3P_F16) ? 1 : 0;
 }
 
 extern "C" int iaf_conv3x3_autotune(iaf_conv3x3_t* c, const float* x, const float* x2, int c_split, int elu_input,
@@ -836,9 +827,9 @@ extern "C" int iaf_conv3x3_autotune(iaf_conv3x3_t* c, const float* x, const floa
     int bsh[4] = {L.nt, L.pxt, L.wco, L.ks};
     int rc = IAF_OK;
     c->bf3_choice = 3;                  // first the exact-fp32 kernel in every shape ...
-    for (int si = 0; si < 8 && rc == IAF_OK; ++si)
+    for (int si = 0; si < (int)std::size(k_conv_shapes) && rc == IAF_OK; ++si)
         for (int nt = 5; nt >= 1 && rc == IAF_OK; --nt) {
-            const int pxt = k_shapes[si][0], wco = k_shapes[si][1], ks = k_shapes[si][2];
+            const int pxt = k_conv_shapes[si].pxt, wco = k_conv_shapes[si].wco, ks = k_conv_shapes[si].ks;
             if (L.ncot % (nt * wco) != 0 || L.nchunk < ks) continue;
             GemmLayer t = L;
             t.nt = nt; t.pxt = pxt; t.wco = wco; t.ks = ks;
@@ -863,11 +854,11 @@ extern "C" int iaf_conv3x3_autotune(iaf_conv3x3_t* c, const float* x, const floa
     int bz[5] = {0, 0, 0, 0, 1};
     if (rc == IAF_OK && L.wp3 && conv_split(c) && !c->mask_mode && !c->deconv) {
         static const int nts[3] = {5, 4, 2};
-        for (int si = 0; si < N_BF3P_SHAPES && rc == IAF_OK; ++si)
+        for (int si = 0; si < (int)std::size(k_bf3p_shapes) && rc == IAF_OK; ++si)
             for (int nt : nts) {
-                const int* sh = k_bf3p_shapes[si];
-                if (!bf3_ragged_ok(L.ncot, nt * sh[3])) continue;
-                L.b_nt = nt; L.b_ppw = sh[0]; L.b_pxt = sh[1]; L.b_ks = sh[2]; L.b_wco = sh[3];
+                const auto& sh = k_bf3p_shapes[si];
+                if (!bf3_ragged_ok(L.ncot, nt * sh.wco)) continue;
+                L.b_nt = nt; L.b_ppw = sh.ppw; L.b_pxt = sh.pxt; L.b_ks = sh.ks; L.b_wco = sh.wco;
                 c->bf3_choice = 2;
                 GemmLayer t = L;
                 if (!conv3x3_bf3_shape(t, 2, (long long)B * H * W, W)) continue;
@@ -882,7 +873,7 @@ extern "C" int iaf_conv3x3_autotune(iaf_conv3x3_t* c, const float* x, const floa
                 if ((rc = (int)hipEventSynchronize(e1)) != 0) break;
                 float ms = 0.f;
                 (void)hipEventElapsedTime(&ms, e0, e1);
-                if (ms < best) { best = ms; bz[0] = nt; bz[1] = sh[0]; bz[2] = sh[1]; bz[3] = sh[2]; bz[4] = sh[3]; }
+                if (ms < best) { best = ms; bz[0] = nt; bz[1] = sh.ppw; bz[2] = sh.pxt; bz[3] = sh.ks; bz[4] = sh.wco; }
             }
         if (bz[0]) { L.b_nt = bz[0]; L.b_ppw = bz[1]; L.b_pxt = bz[2]; L.b_ks = bz[3]; L.b_wco = bz[4]; c->bf3_choice = 2; }
         else c->bf3_choice = 3;
@@ -1153,9 +1144,9 @@ extern "C" int iaf_conv3x3_autotune_backward(iaf_conv3x3_t* c, const float* x, c
     };
     // (the fp32 candidates run with the bf16x3 data gradient switched off: tuned_bf3 = false for this size)
     T.tuned_P = (long long)B * H * W; T.tuned_W = W; T.tuned_bf3 = false;
-    for (int si = 0; si < 8 && rc == IAF_OK; ++si)
+    for (int si = 0; si < (int)std::size(k_conv_shapes) && rc == IAF_OK; ++si)
         for (int nt = 5; nt >= 1 && rc == IAF_OK; --nt) {
-            const int pxt = k_shapes[si][0], wco = k_shapes[si][1], ks = k_shapes[si][2];
+            const int pxt = k_conv_shapes[si].pxt, wco = k_conv_shapes[si].wco, ks = k_conv_shapes[si].ks;
             if (T.ncot % (nt * wco) != 0 || T.nchunk < ks) continue;
             GemmLayer t = T;
             t.nt = nt; t.pxt = pxt; t.wco = wco; t.ks = ks;

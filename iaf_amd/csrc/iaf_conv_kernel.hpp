@@ -732,3 +732,5 @@ __global__ __launch_bounds__(64 * PXT * WCO * KS) void iaf_conv_kernel(ConvP p) 
 }
 
 typedef void (*conv_fn_t)(ConvP);
+// forms of the 9-tap plain conv (iaf_conv_bf3_plain_inst.hip: one picker per launch shape, iaf_pick_bf3p_*(nt, form))
+enum { BF3P_PLAIN, BF3P_DGRAD, BF3P_F16, BF3P_F16_DGRAD, BF3P_PRIOR, BF3P_PRIOR_F16, BF3P_S2, BF3P_DECONV };

@@ -41,6 +41,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <iterator>
 #include <map>
 #include <mutex>
 #include <new>
@@ -165,7 +166,7 @@ struct iaf_stack {
 //    themselves.  It is filled synchronously AT CAPTURE TIME on a private stream (capture mode relaxed around the copy), so
 //    the graph carries no copy node (round 3 first recorded one: 4.9 us per replay of a 475 us step); if the runtime refuses
 //    that, the copy is captured from the slot's own pinned snapshot instead.  Either way a replay neither reads a recycled
-//    snapshot nor overwrites the table the eager runs keep in sync with their host copy.
+//    snapshot nor overwrites the table the eager runs keep equal to their host copy.
 #define PREP_RING 4
 #define PREP_CAPTURE_SLOTS 16
 struct DescTable {
@@ -256,112 +257,71 @@ static int desc_upload(DescTable* t, const void* host, bool changed, hipStream_t
     return IAF_OK;
 }
 
-// one translation unit per launch shape (iaf_conv_inst.hip, compiled with -DIAF_PXT/-DIAF_WCO/-DIAF_KS)
-#define IAF_DECL_SHAPE(P, W, K) extern "C" conv_fn_t iaf_pick_conv_##P##_##W##_##K(int nt, int inmode, int epi);
-IAF_DECL_SHAPE(4, 1, 1)
-IAF_DECL_SHAPE(4, 1, 2)
-IAF_DECL_SHAPE(2, 2, 1)
-IAF_DECL_SHAPE(2, 2, 2)
-IAF_DECL_SHAPE(2, 1, 2)
-IAF_DECL_SHAPE(2, 1, 4)
-IAF_DECL_SHAPE(1, 1, 4)
-IAF_DECL_SHAPE(1, 2, 2)
+// The compiled launch shapes (iaf_variants.def), one translation unit each: a table per family of {shape, picker}, in search order.
+// exact-fp32 masked / plain conv (iaf_conv_inst.hip)
+#define IAF_CONV(P, W, K) extern "C" conv_fn_t iaf_pick_conv_##P##_##W##_##K(int nt, int inmode, int epi);
+// bf16x3 masked conv (iaf_conv_bf3_inst.hip)
+#define IAF_BF3(P, X, K, C) extern "C" conv_fn_t iaf_pick_bf3_##P##_##X##_##K##_##C(int nt, int inmode, int epi);
+// 9-tap plain conv on the matrix cores (iaf_conv_bf3_plain_inst.hip): form = BF3P_*
+#define IAF_BF3P(P, X, K, C, S2) extern "C" conv_fn_t iaf_pick_bf3p_##P##_##X##_##K##_##C(int nt, int form);
+#include "iaf_variants.def"
 
-// bf16x3 kernels (iaf_conv_bf3.hpp), one translation unit per (ppw, pxt, ks, wco)
-#define IAF_DECL_BF3(P, X, K, C) extern "C" conv_fn_t iaf_pick_bf3_##P##_##X##_##K##_##C(int nt, int inmode, int epi);
-IAF_DECL_BF3(4, 1, 4, 1)
-IAF_DECL_BF3(2, 1, 4, 1)
-IAF_DECL_BF3(1, 1, 4, 1)
-IAF_DECL_BF3(1, 4, 1, 1)
-IAF_DECL_BF3(2, 1, 4, 2)
-IAF_DECL_BF3(1, 1, 4, 2)
-#define N_BF3_SHAPES 6
-static const int k_bf3_shapes[N_BF3_SHAPES][4] = {{4, 1, 4, 1}, {2, 1, 4, 1}, {1, 1, 4, 1}, {1, 4, 1, 1}, {2, 1, 4, 2}, {1, 1, 4, 2}};   // keep in sync with iaf_amd/build.py
-static conv_fn_t pick_bf3(int nt, int ppw, int pxt, int ks, int inmode, int epi, int wco = 1) {
-    if (ppw == 4 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3_4_1_4_1(nt, inmode, epi);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3_2_1_4_1(nt, inmode, epi);
-    if (ppw == 1 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3_1_1_4_1(nt, inmode, epi);
-    if (ppw == 1 && pxt == 4 && ks == 1 && wco == 1) return iaf_pick_bf3_1_4_1_1(nt, inmode, epi);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 2) return iaf_pick_bf3_2_1_4_2(nt, inmode, epi);
-    if (ppw == 1 && pxt == 1 && ks == 4 && wco == 2) return iaf_pick_bf3_1_1_4_2(nt, inmode, epi);
+static const struct { int pxt, wco, ks; conv_fn_t (*pick)(int, int, int); } k_conv_shapes[] = {
+#define IAF_CONV(P, W, K) {P, W, K, iaf_pick_conv_##P##_##W##_##K},
+#include "iaf_variants.def"
+};
+static const struct { int ppw, pxt, ks, wco; conv_fn_t (*pick)(int, int, int); } k_bf3_shapes[] = {
+#define IAF_BF3(P, X, K, C) {P, X, K, C, iaf_pick_bf3_##P##_##X##_##K##_##C},
+#include "iaf_variants.def"
+};
+static const struct { int ppw, pxt, ks, wco; conv_fn_t (*pick)(int, int); } k_bf3p_shapes[] = {
+#define IAF_BF3P(P, X, K, C, S2) {P, X, K, C, iaf_pick_bf3p_##P##_##X##_##K##_##C},
+#include "iaf_variants.def"
+};
+
+static conv_fn_t pick_kernel(int nt, int pxt, int wco, int ks, int inmode, int epi) {
+    if (nt < 1 || nt > 5) return nullptr;
+    for (const auto& sh : k_conv_shapes)
+        if (sh.pxt == pxt && sh.wco == wco && sh.ks == ks) return sh.pick(nt, inmode, epi);
     return nullptr;
 }
+static conv_fn_t pick_bf3(int nt, int ppw, int pxt, int ks, int inmode, int epi, int wco = 1) {
+    for (const auto& sh : k_bf3_shapes)
+        if (sh.ppw == ppw && sh.pxt == pxt && sh.ks == ks && sh.wco == wco) return sh.pick(nt, inmode, epi);
+    return nullptr;
+}
+static conv_fn_t pick_bf3p(int nt, int ppw, int pxt, int ks, int wco, int form) {
+    for (const auto& sh : k_bf3p_shapes)
+        if (sh.ppw == ppw && sh.pxt == pxt && sh.ks == ks && sh.wco == wco) return sh.pick(nt, form);
+    return nullptr;
+}
+
+// The one-launch step kernel for a key (iaf_step_fused_types.hpp): every part of iaf_variants.def is asked; at most one answers.
+static step_fn_t (*const k_step_parts[])(const StepKey&, size_t*, size_t*) = {
+#define IAF_STEP_PART(part) iaf_pick_step_part_##part,
+#include "iaf_variants.def"
+};
+static step_fn_t pick_step(const StepKey& k, size_t* lds, size_t* row) {
+    for (auto part : k_step_parts)
+        if (step_fn_t f = part(k, lds, row)) return f;
+    return nullptr;
+}
+// the statement of the operator as the step kernels' var
+static int step_var(const iaf_stack_t* s) { return s->variant == IAF_VARIANT_TF ? 0 : s->variant == IAF_VARIANT_THEANO ? 1 : 2; }
+static StepKey step_key(const iaf_stack_t* s, int W, int R, int form, int planes = STEP_BF16X3) {
+    return StepKey{s->n_h / 16, s->n_z / 16, s->depth_ar, W, R, step_var(s), form, planes};
+}
+
 static size_t bf3_lds_bytes(int cin, int W, int nt, int ppw, int pxt, int ks, int wco = 1) {
     const size_t tile = (size_t)(16 * ppw * pxt + W + 1 + 1) * (3 * (cin / 8) + 2) * 16;
     const size_t red = ks > 1 ? (size_t)pxt * wco * ks * ppw * nt * 1024 : 0;     // split-K exchange aliases the (dead) tile
     return tile > red ? tile : red;
-}
-
-// 9-tap plain convs on the bf16 matrix cores (iaf_conv_bf3_plain_inst.hip): shapes (ppw, pxt, ks, wco); keep in sync with build.py
-// (2, 1, 4, 3), round 6: THREE co groups of NT tiles on one staged tile (768 threads, three waves per SIMD: NT = 2 / 4 only) -- the 24 output
-// tiles of up_conv1 (160 -> 384) in two workgroups per pixel block instead of three
-#define N_BF3P_SHAPES 4
-static const int k_bf3p_shapes[N_BF3P_SHAPES][4] = {{2, 1, 4, 1}, {4, 1, 4, 1}, {2, 1, 4, 2}, {2, 1, 4, 3}};
-extern "C" conv_fn_t iaf_pick_bf3p_2_1_4_1(int nt, int epi);
-extern "C" conv_fn_t iaf_pick_bf3p_4_1_4_1(int nt, int epi);
-extern "C" conv_fn_t iaf_pick_bf3p_2_1_4_2(int nt, int epi);
-extern "C" conv_fn_t iaf_pick_bf3p_2_1_4_3(int nt, int epi);
-static conv_fn_t pick_bf3_plain(int nt, int ppw, int pxt, int ks, int wco, int epi = EPI_PLAIN) {
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3p_2_1_4_1(nt, epi);
-    if (ppw == 4 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3p_4_1_4_1(nt, epi);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 2) return iaf_pick_bf3p_2_1_4_2(nt, epi);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 3) return iaf_pick_bf3p_2_1_4_3(nt, epi);
-    return nullptr;
-}
-extern "C" conv_fn_t iaf_pick_bf3p16_2_1_4_1(int nt);
-extern "C" conv_fn_t iaf_pick_bf3p16_4_1_4_1(int nt);
-extern "C" conv_fn_t iaf_pick_bf3p16_2_1_4_2(int nt);
-extern "C" conv_fn_t iaf_pick_bf3p16_2_1_4_3(int nt);
-extern "C" conv_fn_t iaf_pick_bf3p16d_2_1_4_1(int nt);
-extern "C" conv_fn_t iaf_pick_bf3p16d_4_1_4_1(int nt);
-extern "C" conv_fn_t iaf_pick_bf3p16d_2_1_4_2(int nt);
-extern "C" conv_fn_t iaf_pick_bf3p16d_2_1_4_3(int nt);
-// ... the data gradient on two fp16 planes (iaf_conv_bf3.hpp DG16)
-static conv_fn_t pick_bf3_plain_f16d(int nt, int ppw, int pxt, int ks, int wco) {
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3p16d_2_1_4_1(nt);
-    if (ppw == 4 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3p16d_4_1_4_1(nt);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 2) return iaf_pick_bf3p16d_2_1_4_2(nt);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 3) return iaf_pick_bf3p16d_2_1_4_3(nt);
-    return nullptr;
-}
-static conv_fn_t pick_bf3_plain_f16(int nt, int ppw, int pxt, int ks, int wco) {
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3p16_2_1_4_1(nt);
-    if (ppw == 4 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3p16_4_1_4_1(nt);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 2) return iaf_pick_bf3p16_2_1_4_2(nt);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 3) return iaf_pick_bf3p16_2_1_4_3(nt);
-    return nullptr;
-}
-extern "C" conv_fn_t iaf_pick_bf3pz_2_1_4_1(int nt, int f16);
-extern "C" conv_fn_t iaf_pick_bf3pz_4_1_4_1(int nt, int f16);
-extern "C" conv_fn_t iaf_pick_bf3pz_2_1_4_2(int nt, int f16);
-extern "C" conv_fn_t iaf_pick_bf3pz_2_1_4_3(int nt, int f16);
-// ... down_conv1 in prior form (EPI_PRIOR, iaf_conv3x3_forward_prior_sample), on bf16 (f16 = 0) or two fp16 planes (f16 = 1)
-static conv_fn_t pick_bf3_prior(int nt, int ppw, int pxt, int ks, int wco, int f16) {
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3pz_2_1_4_1(nt, f16);
-    if (ppw == 4 && pxt == 1 && ks == 4 && wco == 1) return iaf_pick_bf3pz_4_1_4_1(nt, f16);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 2) return iaf_pick_bf3pz_2_1_4_2(nt, f16);
-    if (ppw == 2 && pxt == 1 && ks == 4 && wco == 3) return iaf_pick_bf3pz_2_1_4_3(nt, f16);
-    return nullptr;
 }
 // LDS of a 9-tap bf16x3 launch: the pixel tile with a halo of W + 1 slots on BOTH sides (+ the zero slot)
 static size_t bf3_plain_lds_bytes(int cin, int W, int nt, int ppw, int pxt, int ks, int wco, int npl = 3) {
     const size_t tile = (size_t)(16 * ppw * pxt + 2 * (W + 1) + 1) * (npl * (cin / 8) + 2) * 16;
     const size_t red = ks > 1 ? (size_t)pxt * wco * ks * ppw * nt * 1024 : 0;
     return tile > red ? tile : red;
-}
-
-// the launch shapes that are compiled: (pxt, wco, ks)
-static conv_fn_t pick_kernel(int nt, int pxt, int wco, int ks, int inmode, int epi) {
-    if (nt < 1 || nt > 5) return nullptr;
-    if (pxt == 4 && wco == 1 && ks == 1) return iaf_pick_conv_4_1_1(nt, inmode, epi);
-    if (pxt == 4 && wco == 1 && ks == 2) return iaf_pick_conv_4_1_2(nt, inmode, epi);
-    if (pxt == 2 && wco == 2 && ks == 1) return iaf_pick_conv_2_2_1(nt, inmode, epi);
-    if (pxt == 2 && wco == 2 && ks == 2) return iaf_pick_conv_2_2_2(nt, inmode, epi);
-    if (pxt == 2 && wco == 1 && ks == 2) return iaf_pick_conv_2_1_2(nt, inmode, epi);
-    if (pxt == 2 && wco == 1 && ks == 4) return iaf_pick_conv_2_1_4(nt, inmode, epi);
-    if (pxt == 1 && wco == 1 && ks == 4) return iaf_pick_conv_1_1_4(nt, inmode, epi);
-    if (pxt == 1 && wco == 2 && ks == 2) return iaf_pick_conv_1_2_2(nt, inmode, epi);
-    return nullptr;
 }
 
 static size_t conv_lds_bytes(const GemmLayer& L, int W) {
@@ -492,8 +452,8 @@ extern "C" int iaf_stack_create(iaf_stack_t** out, int n_z, int n_h, int depth_a
     if (!generic && variant == IAF_VARIANT_TF) {
         static const bool f16_default = !(getenv("IAF_DEFAULT_PRECISION") && !strcmp(getenv("IAF_DEFAULT_PRECISION"), "bf16x3"));
         size_t l16 = 0, x16 = 0;
-        if (f16_default && (iaf_pick_step_fused_f16(n_h / 16, n_z / 16, depth_ar, 16, 2, 0, 1, &l16, &x16) ||
-                            iaf_pick_step_fused_f16(n_h / 16, n_z / 16, depth_ar, 8, 1, 0, 0, &l16, &x16))) {
+        if (f16_default && (pick_step(step_key(s, 16, 2, STEP_XCH, STEP_F16X2), &l16, &x16) ||
+                            pick_step(step_key(s, 8, 1, STEP_HELPERS, STEP_F16X2), &l16, &x16))) {
             int rc = iaf_stack_set_precision(s, IAF_PRECISION_F16X2);
             if (rc != IAF_OK && rc != IAF_ERR_UNSUPPORTED) { iaf_stack_destroy(s); return rc; }
         }
@@ -961,14 +921,12 @@ static int carve_ws(const iaf_stack_t* s, int B, int H, int W, void* ws, size_t 
 // 256 CUs), so the shape is chosen to minimise the longest per-SIMD MFMA chain:
 //   cycles(wave) = (5*nchunk/ks) steps * nt tiles * 4 MFMA * 32 cycles;  waves sharing a SIMD serialise;
 //   T = rounds over the 256 CUs * (cycles(WG) + fixed prologue/epilogue cost).
-// Ties go to fewer rounds, then less split-K, then bigger tiles (more operand reuse).
-static const int k_shapes[][3] = {{4, 1, 1}, {2, 2, 1}, {4, 1, 2}, {2, 2, 2}, {2, 1, 2}, {1, 2, 2}, {2, 1, 4}, {1, 1, 4}};
-
+// Ties go to fewer rounds, then less split-K, then bigger tiles (more operand reuse), then the earlier shape of k_conv_shapes.
 static void auto_shape(GemmLayer& L, bool is_out, long long P, int W) {
     double best = 1e30;
     int bnt = 0, bs = -1;
-    for (int si = 0; si < 8; ++si) {
-        const int pxt = k_shapes[si][0], wco = k_shapes[si][1], ks = k_shapes[si][2];
+    for (int si = 0; si < (int)std::size(k_conv_shapes); ++si) {
+        const int pxt = k_conv_shapes[si].pxt, wco = k_conv_shapes[si].wco, ks = k_conv_shapes[si].ks;
         if (L.nchunk < ks) continue;
         for (int nt = 5; nt >= 1; --nt) {
             if (is_out && (nt & 1)) continue;
@@ -985,7 +943,7 @@ static void auto_shape(GemmLayer& L, bool is_out, long long P, int W) {
             if (T < best) { best = T; bnt = nt; bs = si; }
         }
     }
-    if (bs >= 0) { L.nt = bnt; L.pxt = k_shapes[bs][0]; L.wco = k_shapes[bs][1]; L.ks = k_shapes[bs][2]; }
+    if (bs >= 0) { L.nt = bnt; L.pxt = k_conv_shapes[bs].pxt; L.wco = k_conv_shapes[bs].wco; L.ks = k_conv_shapes[bs].ks; }
 }
 
 // raise the dynamic-LDS cap once per kernel (never inside a stream capture: warm up first)
@@ -1216,11 +1174,7 @@ static int run_stack_generic(iaf_stack_t* s, const ConvP& base, int first_inmode
 static step_fn_t fused_step_xch(const iaf_stack_t* s, int H, int W, int R, size_t* lds, size_t* xrow) {
     static const bool xch_env = !(getenv("IAF_FUSE_XCH") && getenv("IAF_FUSE_XCH")[0] == '0');
     if (!xch_env || !s->xch_on || R <= 0 || (H + R - 1) / R < 2) return nullptr;
-    const int var = s->variant == IAF_VARIANT_TF ? 0 : s->variant == IAF_VARIANT_THEANO ? 1 : 2;
-    step_fn_t f = iaf_pick_step_fused_xch(s->n_h / 16, s->n_z / 16, s->depth_ar, W, R, var, lds, xrow);
-    if (!f) f = iaf_pick_step_fused_xch_b(s->n_h / 16, s->n_z / 16, s->depth_ar, W, R, var, lds, xrow);
-    if (!f) f = iaf_pick_step_fused_xch_c(s->n_h / 16, s->n_z / 16, s->depth_ar, W, R, var, lds, xrow);
-    if (!f) f = iaf_pick_step_fused_xch_d(s->n_h / 16, s->n_z / 16, s->depth_ar, W, R, var, lds, xrow);
+    step_fn_t f = pick_step(step_key(s, W, R, STEP_XCH), lds, xrow);
     return (f && *lds <= 160 * 1024) ? f : nullptr;
 }
 
@@ -1234,8 +1188,7 @@ static step_fn_t fused_step_pair(const iaf_stack_t* s, int W, size_t* lds, size_
     // with its loads and LDS reads), not by the port, and the hand-over exposes 3.9 k cycles (profiles/r05/experiments/pair_form.txt).
     static const bool pair_env = getenv("IAF_FUSE_PAIR") && getenv("IAF_FUSE_PAIR")[0] == '1';
     if (!(pair_env || (s->xch_knob & 32u)) || !s->xch_on || W != 8) return nullptr;
-    const int var = s->variant == IAF_VARIANT_TF ? 0 : s->variant == IAF_VARIANT_THEANO ? 1 : 2;
-    step_fn_t f = iaf_pick_step_fused_pair(s->n_h / 16, s->n_z / 16, s->depth_ar, W, 2, var, lds, prow);
+    step_fn_t f = pick_step(step_key(s, W, 2, STEP_PAIR), lds, prow);
     return (f && *lds <= 160 * 1024) ? f : nullptr;
 }
 
@@ -1323,21 +1276,21 @@ static step_fn_t fused_step_plan(const iaf_stack_t* s, int B, int H, int W, int*
             if (wmb * 12.3 > 4.6 * s->nlayers) return nullptr;
         }
     }
-    const int var = s->variant == IAF_VARIANT_TF ? 0 : s->variant == IAF_VARIANT_THEANO ? 1 : 2;
     if (!forceR || forceR == 2) {
         // 8-pixel rows: the pair form (R = 2 rows per PAIR of workgroups).  Without buffers for it (a capture that was not warmed up)
         // launch_fused_step runs the recomputing kernel of the same R instead.
         size_t pl = 0, prow = 0;
         if (step_fn_t fp = fused_step_pair(s, W, &pl, &prow)) {
-            size_t rl = 0;
-            if (iaf_pick_step_fused(s->n_h / 16, s->n_z / 16, s->depth_ar, W, 2, var, &rl) && rl <= 160 * 1024) {
+            size_t rl = 0, rr = 0;
+            if (pick_step(step_key(s, W, 2, STEP_RECOMPUTE), &rl, &rr) && rl <= 160 * 1024) {
                 if (launching) (void)xch_prepare(const_cast<iaf_stack_t*>(s), B, (H + 1) / 2, prow, st);
                 *R = 2; *lds = pl;
                 return fp;
             }
         }
     }
-    step_fn_t fn = iaf_pick_step_fused(s->n_h / 16, s->n_z / 16, s->depth_ar, W, *R, var, lds);
+    size_t row = 0;
+    step_fn_t fn = pick_step(step_key(s, W, *R, STEP_RECOMPUTE), lds, &row);
     if (fn && *lds <= 160 * 1024) return fn;               // (launch_fused_step switches to the halo-exchange form where it applies)
     // geometries whose LDS regions only fit in the halo-exchange form (R + 1 rows per region instead of R + depth_ar): config 3's
     // n_h = 128 / 192 at 16-pixel rows
@@ -1363,11 +1316,10 @@ extern "C" int iaf_stack_step_is_f16(const iaf_stack_t* s, int B, int H, int W) 
     if (!s || B <= 0 || H <= 0 || W <= 0 || !f16_active(s)) return 0;
     const int R = iaf_stack_step_is_fused(s, B, H, W);
     if (R <= 0 || iaf_stack_step_pairs(s, B, H, W)) return 0;
-    const int var = s->variant == IAF_VARIANT_TF ? 0 : s->variant == IAF_VARIANT_THEANO ? 1 : 2;
     size_t l = 0, x = 0, xl = 0, xr = 0;
-    if (fused_step_xch(s, H, W, R, &xl, &xr)) return iaf_pick_step_fused_f16(s->n_h / 16, s->n_z / 16, s->depth_ar, W, R, var, 1, &l, &x) ? 1 : 0;
+    if (fused_step_xch(s, H, W, R, &xl, &xr)) return pick_step(step_key(s, W, R, STEP_XCH, STEP_F16X2), &l, &x) ? 1 : 0;
     static const int h8_env = getenv("IAF_STEP_HELPERS") ? atoi(getenv("IAF_STEP_HELPERS")) : -1;
-    return (h8_env != 0 && iaf_pick_step_fused_f16(s->n_h / 16, s->n_z / 16, s->depth_ar, W, R, var, 0, &l, &x)) ? 1 : 0;
+    return (h8_env != 0 && pick_step(step_key(s, W, R, STEP_HELPERS, STEP_F16X2), &l, &x)) ? 1 : 0;
 }
 
 extern "C" int iaf_stack_step_exchanges(const iaf_stack_t* s, int B, int H, int W) {
@@ -1413,7 +1365,6 @@ static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, co
         return IAF_ERR_RANGE;
     }
     const bool f16 = f16_active(s);
-    const int var_i = s->variant == IAF_VARIANT_TF ? 0 : s->variant == IAF_VARIANT_THEANO ? 1 : 2;
     bool f16_fn = false;                                     // the launch runs an F16 kernel (on the two-plane packs)
     StepP q;
     memset(&q, 0, sizeof(q));
@@ -1446,8 +1397,8 @@ static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, co
                 pair = true; lds = pl;
                 q.xh = x->buf; q.xctl = x->ctl; q.xerr = s->xch_err_dev; q.xknob = s->xch_knob;
             } else {                                         // no buffers (inside a capture that was not warmed up): the recomputing kernel of the same R
-                const int var = s->variant == IAF_VARIANT_TF ? 0 : s->variant == IAF_VARIANT_THEANO ? 1 : 2;
-                fn = iaf_pick_step_fused(s->n_h / 16, s->n_z / 16, s->depth_ar, base.W, R, var, &lds);
+                size_t row = 0;
+                fn = pick_step(step_key(s, base.W, R, STEP_RECOMPUTE), &lds, &row);
                 if (!fn) return IAF_ERR_NOT_PREPARED;
             }
         }
@@ -1457,7 +1408,7 @@ static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, co
         if (step_fn_t fx = fused_step_xch(s, base.H, base.W, R, &xl, &xrow)) {
             // the exchange form on fp16 planes, where the stack asks for it and the geometry is compiled: rows of two planes, a set of its own
             size_t xl16 = 0, xrow16 = 0;
-            step_fn_t fx16 = f16 ? iaf_pick_step_fused_f16(s->n_h / 16, s->n_z / 16, s->depth_ar, base.W, R, var_i, 1, &xl16, &xrow16) : nullptr;
+            step_fn_t fx16 = f16 ? pick_step(step_key(s, base.W, R, STEP_XCH, STEP_F16X2), &xl16, &xrow16) : nullptr;
             iaf_stack::XchSet* x16 = fx16 ? xch_prepare(s, base.B, q.nrb, xrow16, st, IAF_XSENT_F16) : nullptr;
             if (x16) {
                 fn = fx16; lds = xl16; f16_fn = true;
@@ -1477,13 +1428,12 @@ static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, co
     // without helpers, 16.89 with).  IAF_STEP_HELPERS=0 keeps the four-wave form (knob 16 only moves the free-bits finish into its own launch).
     static const int h8_env = getenv("IAF_STEP_HELPERS") ? atoi(getenv("IAF_STEP_HELPERS")) : -1;
     if (h8_env != 0 && !q.xh && !pair) {
-        size_t hl = 0;
-        const int var = s->variant == IAF_VARIANT_TF ? 0 : s->variant == IAF_VARIANT_THEANO ? 1 : 2;
-        if (step_fn_t fh = iaf_pick_step_fused_h(s->n_h / 16, s->n_z / 16, s->depth_ar, base.W, R, var, &hl))
+        size_t hl = 0, hr = 0;
+        if (step_fn_t fh = pick_step(step_key(s, base.W, R, STEP_HELPERS), &hl, &hr))
             if (hl == lds) fn = fh;
         // ... on fp16 planes (its own LDS layout: two planes per slot)
         size_t hl16 = 0, xr16 = 0;
-        if (step_fn_t fh16 = f16 ? iaf_pick_step_fused_f16(s->n_h / 16, s->n_z / 16, s->depth_ar, base.W, R, var, 0, &hl16, &xr16) : nullptr) {
+        if (step_fn_t fh16 = f16 ? pick_step(step_key(s, base.W, R, STEP_HELPERS, STEP_F16X2), &hl16, &xr16) : nullptr) {
             fn = fh16; lds = hl16; f16_fn = true;
         }
     }
@@ -1639,10 +1589,10 @@ extern "C" int iaf_stack_autotune(iaf_stack_t* s, const float* z, const float* c
             const bool ut = L.b_user_tuned;
             const int sv[5] = {L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco};
             static const int nts[3] = {5, 4, 2};
-            for (int si = 0; si < N_BF3_SHAPES && !rc; ++si)
+            for (int si = 0; si < (int)std::size(k_bf3_shapes) && !rc; ++si)
                 for (int ni = 0; ni < 3 && !rc; ++ni) {
-                    const int nt = nts[ni], ppw = k_bf3_shapes[si][0], pxt = k_bf3_shapes[si][1], ks = k_bf3_shapes[si][2];
-                    const int wco = k_bf3_shapes[si][3];
+                    const int nt = nts[ni], ppw = k_bf3_shapes[si].ppw, pxt = k_bf3_shapes[si].pxt, ks = k_bf3_shapes[si].ks;
+                    const int wco = k_bf3_shapes[si].wco;
                     if (L.ncot % (nt * wco) != 0 || (is_out && (nt & 1))) continue;
                     if (!pick_bf3(nt, ppw, pxt, ks, IN_PIXMAJOR, is_out ? EPI_OUT : EPI_HIDDEN, wco)) continue;
                     if (bf3_lds_bytes(L.cin, W, nt, ppw, pxt, ks, wco) > 160 * 1024) continue;
@@ -1723,13 +1673,13 @@ extern "C" int iaf_stack_autotune(iaf_stack_t* s, const float* z, const float* c
         float best = 1e30f, ms = 0.f;
         int bz[5] = {0, 0, 0, 0, 1};
         static const int nts[3] = {5, 4, 2};
-        for (int si = 0; si < N_BF3_SHAPES && !rc; ++si)
+        for (int si = 0; si < (int)std::size(k_bf3_shapes) && !rc; ++si)
             for (int ni = 0; ni < 3 && !rc; ++ni) {
                 const int nt = nts[ni];
-                const int* sh = k_bf3_shapes[si];
-                if (!fuse_shape_ok(s, nt, sh[0], sh[1], sh[2], sh[3], W)) continue;
+                const auto& sh = k_bf3_shapes[si];
+                if (!fuse_shape_ok(s, nt, sh.ppw, sh.pxt, sh.ks, sh.wco, W)) continue;
                 L1.fz_P = P; L1.fz_W = W; L1.fz_on = true;
-                L1.fz[0] = nt; L1.fz[1] = sh[0]; L1.fz[2] = sh[1]; L1.fz[3] = sh[2]; L1.fz[4] = sh[3];
+                L1.fz[0] = nt; L1.fz[1] = sh.ppw; L1.fz[2] = sh.pxt; L1.fz[3] = sh.ks; L1.fz[4] = sh.wco;
                 s->fuse_first = 2;
                 rc = iaf_step_time_layer(s, -1, z, context, z_new, logsd, B, H, W, workspace, workspace_bytes, reps, stream, &ms);
                 if (rc == IAF_ERR_UNSUPPORTED) { rc = IAF_OK; continue; }

@@ -1,8 +1,12 @@
 // iaf_step_fused_inst.hip -- instantiations of the one-launch IAF step (iaf_step_fused.hpp) for the geometries the
 // BASELINE configs use: n_h = 160 / n_z = 32 / depth_ar = 2 (configs 1-2, 5: README run) and n_h = 64 / depth_ar = 1
 // (config 0), images 16, 8 and 4 pixels wide (4-pixel rows: one workgroup per four rows, i.e. per 4x4 image); and for the deep
-// stack of config 3 (n_z = 64, depth_ar = 4, n_h = 64 / 128 / 192) wherever its five LDS regions fit 160 KiB.  Built as its own translation unit by iaf_amd/build.py.
+// stack of config 3 (n_z = 64, depth_ar = 4, n_h = 64 / 128 / 192) wherever its five LDS regions fit 160 KiB.  Built one part per translation unit by iaf_amd/build.py.
 #include "iaf_step_fused.hpp"
+
+#ifndef IAF_FUSED_PART
+#error "compile with -DIAF_FUSED_PART=<part of iaf_variants.def>"
+#endif
 
 template <int NHT, int NZT, int DEPTH, int W, int R, int XCH = 0>
 static step_fn_t inst(int var, size_t* lds, size_t* xrow) {
@@ -81,91 +85,76 @@ static step_fn_t inst_wr(int W, int R, int var, size_t* lds) {
     return nullptr;
 }
 
-// two translation units (iaf_amd/build.py: -DIAF_FUSED_PART=0 / 1) so that the build compiles them side by side
-// (no -DIAF_FUSED_PART: both parts in one unit)
-#if !defined(IAF_FUSED_PART) || IAF_FUSED_PART == 0
-// the halo-exchange kernels: the BASELINE run's 16-pixel geometry, all three statements (at 8-pixel rows, one row per workgroup,
-// the exchange costs more than the recompute it saves: 40.6 k against 35.6 k cycles)
-extern "C" step_fn_t iaf_pick_step_fused_xch(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* xrow) {
-    *lds = 0; *xrow = 0;
-    if (nht == 10 && nzt == 2 && depth == 2 && W == 16 && R == 2) return inst<10, 2, 2, 16, 2, 1>(var, lds, xrow);
+static bool at(const StepKey& k, int nht, int nzt, int depth) { return k.nht == nht && k.nzt == nzt && k.depth == depth; }
+
+// one part per translation unit (iaf_amd/build.py: -DIAF_FUSED_PART=<part>, the parts of iaf_variants.def) so that the build compiles
+// them side by side; each part answers its own keys (StepKey), no key is answered by two parts
+#if IAF_FUSED_PART == 0
+static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
+    if (k.planes != STEP_BF16X3) return nullptr;
+    // the halo-exchange kernels: the BASELINE run's 16-pixel geometry, all three statements (at 8-pixel rows, one row per workgroup,
+    // the exchange costs more than the recompute it saves: 40.6 k against 35.6 k cycles)
+    if (k.form == STEP_XCH && at(k, 10, 2, 2) && k.W == 16 && k.R == 2) return inst<10, 2, 2, 16, 2, 1>(k.var, lds, row);
+    // ... with helper waves: the BASELINE run's 8-pixel geometry (same LDS layout as the plain form: call with the plain form's R)
+    if (k.form == STEP_HELPERS && at(k, 10, 2, 2) && k.W == 8) {
+        if (k.R == 1) return inst_h<10, 2, 2, 8, 1>(k.var, lds);
+        if (k.R == 2) return inst_h<10, 2, 2, 8, 2>(k.var, lds);
+    }
+    if (k.form == STEP_RECOMPUTE) {
+        if (at(k, 10, 2, 2)) return inst_wr<10, 2, 2>(k.W, k.R, k.var, lds);      // configs 1-2, 5 (README run)
+        if (at(k, 4, 2, 1)) return inst_wr<4, 2, 1>(k.W, k.R, k.var, lds);        // config 0
+    }
     return nullptr;
 }
-// ... with helper waves: the BASELINE run's 8-pixel geometry (same LDS layout as the plain form: call with the plain form's R)
-extern "C" step_fn_t iaf_pick_step_fused_h(int nht, int nzt, int depth, int W, int R, int var, size_t* lds) {
-    *lds = 0;
-    if (nht == 10 && nzt == 2 && depth == 2 && W == 8 && R == 1) return inst_h<10, 2, 2, 8, 1>(var, lds);
-    if (nht == 10 && nzt == 2 && depth == 2 && W == 8 && R == 2) return inst_h<10, 2, 2, 8, 2>(var, lds);
-    return nullptr;
-}
-extern "C" step_fn_t iaf_pick_step_fused_a(int nht, int nzt, int depth, int W, int R, int var, size_t* lds) {
-    *lds = 0;
-    if (nht == 10 && nzt == 2 && depth == 2) return inst_wr<10, 2, 2>(W, R, var, lds);      // configs 1-2, 5 (README run)
-    if (nht == 4 && nzt == 2 && depth == 1) return inst_wr<4, 2, 1>(W, R, var, lds);        // config 0
-    return nullptr;
-}
-#endif
-#if !defined(IAF_FUSED_PART) || IAF_FUSED_PART == 2
+#elif IAF_FUSED_PART == 2
 // depth_ar = 3 (models.py:92 allows any depth; README.md:49 sweeps it): the n_z = 32 families of configs 0-2.  Hidden layers ping-pong
 // between the two LDS regions, so an odd depth is the same code (the output pair's exchange buffer moves: StepGeom::XB_OFF).
-extern "C" step_fn_t iaf_pick_step_fused_xch_c(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* xrow) {
-    *lds = 0; *xrow = 0;
-    if (nht == 10 && nzt == 2 && depth == 3 && W == 16 && R == 2) return inst<10, 2, 3, 16, 2, 1>(var, lds, xrow);
-    return nullptr;
-}
-extern "C" step_fn_t iaf_pick_step_fused_c(int nht, int nzt, int depth, int W, int R, int var, size_t* lds) {
-    *lds = 0;
-    if (nht == 10 && nzt == 2 && depth == 3) return inst_wr<10, 2, 3>(W, R, var, lds);
-    if (nht == 4 && nzt == 2 && depth == 3) return inst_wr<4, 2, 3>(W, R, var, lds);
-    return nullptr;
-}
-#endif
-#if !defined(IAF_FUSED_PART) || IAF_FUSED_PART == 1
-// config 3 (up_iaf2_nl, n_z = 64, depth_ar = 4; n_h is not fixed by the reference's scripts, SURVEY D5): the geometries that fit
-// ... in the halo-exchange form: the regions hold R + 1 rows instead of R + depth_ar, which is what lets n_h = 128 / 192 fit
-// 160 KiB at 16-pixel rows (150 KiB at n_h = 192; the recomputing form needs 210)
-extern "C" step_fn_t iaf_pick_step_fused_xch_b(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* xrow) {
-    *lds = 0; *xrow = 0;
-    if (nzt == 4 && depth == 4 && W == 16 && R == 2) {
-        if (nht == 4) return inst<4, 4, 4, 16, 2, 1>(var, lds, xrow);
-        if (nht == 8) return inst<8, 4, 4, 16, 2, 1>(var, lds, xrow);
-        if (nht == 12) return inst<12, 4, 4, 16, 2, 1>(var, lds, xrow);
+static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
+    if (k.planes != STEP_BF16X3) return nullptr;
+    if (k.form == STEP_XCH && at(k, 10, 2, 3) && k.W == 16 && k.R == 2) return inst<10, 2, 3, 16, 2, 1>(k.var, lds, row);
+    if (k.form == STEP_RECOMPUTE) {
+        if (at(k, 10, 2, 3)) return inst_wr<10, 2, 3>(k.W, k.R, k.var, lds);
+        if (at(k, 4, 2, 3)) return inst_wr<4, 2, 3>(k.W, k.R, k.var, lds);
     }
     return nullptr;
 }
-extern "C" step_fn_t iaf_pick_step_fused_b(int nht, int nzt, int depth, int W, int R, int var, size_t* lds) {
-    *lds = 0;
-    if (nht == 4 && nzt == 4 && depth == 4) return inst_wr<4, 4, 4>(W, R, var, lds);
-    if (nht == 8 && nzt == 4 && depth == 4) return inst_wr<8, 4, 4>(W, R, var, lds);
-    if (nht == 12 && nzt == 4 && depth == 4) return inst_wr<12, 4, 4>(W, R, var, lds);
+#elif IAF_FUSED_PART == 1
+// config 3 (up_iaf2_nl, n_z = 64, depth_ar = 4; n_h is not fixed by the reference's scripts, SURVEY D5): the geometries that fit
+static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
+    if (k.planes != STEP_BF16X3) return nullptr;
+    // ... in the halo-exchange form: the regions hold R + 1 rows instead of R + depth_ar, which is what lets n_h = 128 / 192 fit
+    // 160 KiB at 16-pixel rows (150 KiB at n_h = 192; the recomputing form needs 210)
+    if (k.form == STEP_XCH && k.nzt == 4 && k.depth == 4 && k.W == 16 && k.R == 2) {
+        if (k.nht == 4) return inst<4, 4, 4, 16, 2, 1>(k.var, lds, row);
+        if (k.nht == 8) return inst<8, 4, 4, 16, 2, 1>(k.var, lds, row);
+        if (k.nht == 12) return inst<12, 4, 4, 16, 2, 1>(k.var, lds, row);
+    }
+    if (k.form == STEP_RECOMPUTE) {
+        if (at(k, 4, 4, 4)) return inst_wr<4, 4, 4>(k.W, k.R, k.var, lds);
+        if (at(k, 8, 4, 4)) return inst_wr<8, 4, 4>(k.W, k.R, k.var, lds);
+        if (at(k, 12, 4, 4)) return inst_wr<12, 4, 4>(k.W, k.R, k.var, lds);
+    }
     return nullptr;
 }
-#endif
-
-#if !defined(IAF_FUSED_PART) || IAF_FUSED_PART == 3
+#elif IAF_FUSED_PART == 3
 // the pair form: the BASELINE run's 8-pixel geometry (R = 2: the pair's 16 pixels)
-extern "C" step_fn_t iaf_pick_step_fused_pair(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* prow) {
-    *lds = 0; *prow = 0;
-    if (nht == 10 && nzt == 2 && depth == 2 && W == 8 && R == 2) return inst_p<10, 2, 2, 8, 2>(var, lds, prow);
+static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
+    if (k.planes == STEP_BF16X3 && k.form == STEP_PAIR && at(k, 10, 2, 2) && k.W == 8 && k.R == 2) return inst_p<10, 2, 2, 8, 2>(k.var, lds, row);
     return nullptr;
 }
-#endif
-
-#if !defined(IAF_FUSED_PART) || IAF_FUSED_PART == 4
+#elif IAF_FUSED_PART == 4
 // siblings of the README run (round 5; models.py:92 takes any n_h, README.md:49 sweeps the flow's depth): n_z = 32 with depth_ar = 2 at
 // n_h = 64 and n_h = 128 -- the 16-pixel rows in the exchange form, 8- and 4-pixel rows recomputing
-extern "C" step_fn_t iaf_pick_step_fused_xch_d(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* xrow) {
-    *lds = 0; *xrow = 0;
-    if (nzt == 2 && depth == 2 && W == 16 && R == 2) {
-        if (nht == 4) return inst<4, 2, 2, 16, 2, 1>(var, lds, xrow);
-        if (nht == 8) return inst<8, 2, 2, 16, 2, 1>(var, lds, xrow);
+static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
+    if (k.planes != STEP_BF16X3) return nullptr;
+    if (k.form == STEP_XCH && k.nzt == 2 && k.depth == 2 && k.W == 16 && k.R == 2) {
+        if (k.nht == 4) return inst<4, 2, 2, 16, 2, 1>(k.var, lds, row);
+        if (k.nht == 8) return inst<8, 2, 2, 16, 2, 1>(k.var, lds, row);
     }
-    return nullptr;
-}
-extern "C" step_fn_t iaf_pick_step_fused_d(int nht, int nzt, int depth, int W, int R, int var, size_t* lds) {
-    *lds = 0;
-    if (nht == 4 && nzt == 2 && depth == 2) return inst_wr<4, 2, 2>(W, R, var, lds);
-    if (nht == 8 && nzt == 2 && depth == 2) return inst_wr<8, 2, 2>(W, R, var, lds);
+    if (k.form == STEP_RECOMPUTE) {
+        if (at(k, 4, 2, 2)) return inst_wr<4, 2, 2>(k.W, k.R, k.var, lds);
+        if (at(k, 8, 2, 2)) return inst_wr<8, 2, 2>(k.W, k.R, k.var, lds);
+    }
     return nullptr;
 }
 #endif
@@ -198,23 +187,30 @@ static step_fn_t inst_f16_tf(int var, size_t* lds, size_t* xrow) {
     if (xrow) *xrow = XCH ? G::xrow_bytes() : 0;
     return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 0, XCH, 1, 0, 1>;
 }
-#if !defined(IAF_FUSED_PART) || IAF_FUSED_PART == 5
-extern "C" step_fn_t iaf_pick_step_fused_f16_a(int nht, int nzt, int depth, int W, int R, int var, int form, size_t* lds, size_t* xrow) {
-    *lds = 0; *xrow = 0;
-    if (nht != 10 || nzt != 2 || depth != 2) return nullptr;
-    if (form == 1 && W == 16 && R == 2) return inst_f16_tf<10, 2, 2, 16, 2, 1>(var, lds, xrow);
-    if (form == 0 && W == 8 && R == 1) return inst_f16_tf<10, 2, 2, 8, 1, 0>(var, lds, xrow);
-    if (form == 0 && W == 8 && R == 2) return inst_f16_tf<10, 2, 2, 8, 2, 0>(var, lds, xrow);
+#if IAF_FUSED_PART == 5
+static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
+    if (k.planes != STEP_F16X2 || !at(k, 10, 2, 2)) return nullptr;
+    if (k.form == STEP_XCH && k.W == 16 && k.R == 2) return inst_f16_tf<10, 2, 2, 16, 2, 1>(k.var, lds, row);
+    if (k.form == STEP_HELPERS && k.W == 8 && k.R == 1) return inst_f16_tf<10, 2, 2, 8, 1, 0>(k.var, lds, row);
+    if (k.form == STEP_HELPERS && k.W == 8 && k.R == 2) return inst_f16_tf<10, 2, 2, 8, 2, 0>(k.var, lds, row);
     return nullptr;
 }
-#endif
-#if !defined(IAF_FUSED_PART) || IAF_FUSED_PART == 6
+#elif IAF_FUSED_PART == 6
 // config 3 (n_z = 64, depth_ar = 4; n_h = 64 / 128) in the exchange form on fp16 planes, all three statements
-extern "C" step_fn_t iaf_pick_step_fused_f16_b(int nht, int nzt, int depth, int W, int R, int var, int form, size_t* lds, size_t* xrow) {
-    *lds = 0; *xrow = 0;
-    if (nzt != 4 || depth != 4 || form != 1 || W != 16 || R != 2) return nullptr;
-    if (nht == 4) return inst_f16<4, 4, 4, 16, 2, 1>(var, lds, xrow);
-    if (nht == 8) return inst_f16_tf<8, 4, 4, 16, 2, 1>(var, lds, xrow);      // (its Theano variants spill 28 VGPRs: bf16x3 for those)
+static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
+    if (k.planes != STEP_F16X2 || k.form != STEP_XCH || k.W != 16 || k.R != 2) return nullptr;
+    if (at(k, 4, 4, 4)) return inst_f16<4, 4, 4, 16, 2, 1>(k.var, lds, row);
+    if (at(k, 8, 4, 4)) return inst_f16_tf<8, 4, 4, 16, 2, 1>(k.var, lds, row);      // (its Theano variants spill 28 VGPRs: bf16x3 for those)
     return nullptr;            // (n_h = 192: the second accumulator set of three tiles per pixel tile does not fit 256 registers -- bf16x3 there)
 }
 #endif
+
+#define IAF_CAT_(a, b) a##b
+#define IAF_CAT(a, b) IAF_CAT_(a, b)
+
+extern "C" step_fn_t IAF_CAT(iaf_pick_step_part_, IAF_FUSED_PART)(const StepKey& k, size_t* lds, size_t* row) {
+    *lds = 0; *row = 0;
+    step_fn_t f = pick(k, lds, row);
+    if (!f) { *lds = 0; *row = 0; }
+    return f;
+}

@@ -70,30 +70,17 @@ struct StepP {
 #define IAF_XSENT_F16 0xfdfffdffu
 
 typedef void (*step_fn_t)(StepP);
-// kernel + dynamic LDS bytes for (n_h / 16, n_z / 16, depth_ar, image width, output rows per workgroup), or NULL
-// var: 0 TF statement, 1 Theano, 2 Theano with flipmask
-extern "C" step_fn_t iaf_pick_step_fused_a(int nht, int nzt, int depth, int W, int R, int var, size_t* lds);   // depth_ar <= 2 geometries
-extern "C" step_fn_t iaf_pick_step_fused_b(int nht, int nzt, int depth, int W, int R, int var, size_t* lds);   // depth_ar = 4 geometries
-// ... in the halo-exchange form (StepP::xh; *xrow = bytes of one exported row); var as above
-extern "C" step_fn_t iaf_pick_step_fused_xch(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* xrow);
-extern "C" step_fn_t iaf_pick_step_fused_xch_b(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* xrow);   // depth_ar = 4
-extern "C" step_fn_t iaf_pick_step_fused_h(int nht, int nzt, int depth, int W, int R, int var, size_t* lds);   // recomputing form with helper waves
-extern "C" step_fn_t iaf_pick_step_fused_c(int nht, int nzt, int depth, int W, int R, int var, size_t* lds);   // depth_ar = 3 geometries
-extern "C" step_fn_t iaf_pick_step_fused_xch_c(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* xrow);
-// the pair form (two workgroups per (image, row block), *prow = bytes one of them hands the other); R = rows per PAIR
-extern "C" step_fn_t iaf_pick_step_fused_pair(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* prow);
-extern "C" step_fn_t iaf_pick_step_fused_d(int nht, int nzt, int depth, int W, int R, int var, size_t* lds);   // n_z = 32, depth_ar = 2, n_h = 64 / 128
-extern "C" step_fn_t iaf_pick_step_fused_xch_d(int nht, int nzt, int depth, int W, int R, int var, size_t* lds, size_t* xrow);
-// the two-plane fp16 kernels ("f16x2"): form = 0 recomputing with helper waves, 1 halo exchange; *xrow as above (0 for form 0)
-extern "C" step_fn_t iaf_pick_step_fused_f16_a(int nht, int nzt, int depth, int W, int R, int var, int form, size_t* lds, size_t* xrow);
-extern "C" step_fn_t iaf_pick_step_fused_f16_b(int nht, int nzt, int depth, int W, int R, int var, int form, size_t* lds, size_t* xrow);
-static inline step_fn_t iaf_pick_step_fused_f16(int nht, int nzt, int depth, int W, int R, int var, int form, size_t* lds, size_t* xrow) {
-    step_fn_t f = iaf_pick_step_fused_f16_a(nht, nzt, depth, W, R, var, form, lds, xrow);
-    return f ? f : iaf_pick_step_fused_f16_b(nht, nzt, depth, W, R, var, form, lds, xrow);
-}
-static inline step_fn_t iaf_pick_step_fused(int nht, int nzt, int depth, int W, int R, int var, size_t* lds) {
-    step_fn_t f = iaf_pick_step_fused_a(nht, nzt, depth, W, R, var, lds);
-    if (!f) f = iaf_pick_step_fused_b(nht, nzt, depth, W, R, var, lds);
-    if (!f) f = iaf_pick_step_fused_c(nht, nzt, depth, W, R, var, lds);
-    return f ? f : iaf_pick_step_fused_d(nht, nzt, depth, W, R, var, lds);
-}
+
+// Which one-launch step kernel.  iaf_step_fused_inst.hip compiles one picker per part (iaf_variants.def); the parts answer disjoint keys.
+enum { STEP_RECOMPUTE, STEP_HELPERS, STEP_XCH, STEP_PAIR };   // form: recomputing, ... with helper waves, halo exchange (StepP::xh), pair
+enum { STEP_BF16X3, STEP_F16X2 };                           // planes: bf16x3, or two fp16 planes ("f16x2": three part-products per K step)
+struct StepKey {
+    int nht, nzt, depth;   // n_h / 16, n_z / 16, depth_ar
+    int W, R;              // image width, output rows per workgroup (the pair form: per PAIR of workgroups)
+    int var;               // 0 TF statement, 1 Theano, 2 Theano with flipmask
+    int form, planes;
+};
+// the kernel, its dynamic LDS bytes and *row: bytes of one exported row (halo exchange), of what one workgroup hands the other (pair),
+// else 0; or NULL with *lds = *row = 0
+#define IAF_STEP_PART(part) extern "C" step_fn_t iaf_pick_step_part_##part(const StepKey& k, size_t* lds, size_t* row);
+#include "iaf_variants.def"

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import golden_inputs as gi
+from iaf_amd.build import BF3_SHAPES
 from oracle import iaf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -95,9 +96,6 @@ def test_bf16x3_error_is_fp32_grade(amd, shape):
     print("max |raw conv output - fp64 oracle|: bf16x3 %.3g, exact-fp32 MFMA %.3g" % (err["bf16x3"], err["f32"]))
     assert err["f32"] < 2e-5 and err["bf16x3"] < 2e-5                    # both two orders inside the 1e-4 bar ...
     assert err["bf16x3"] <= 2.0 * err["f32"] + 1e-6                      # ... and the split products are no worse
-
-
-BF3_SHAPES = [(4, 1, 4, 1), (2, 1, 4, 1), (1, 1, 4, 1), (1, 4, 1, 1), (2, 1, 4, 2), (1, 1, 4, 2)]
 
 
 @pytest.mark.parametrize("shp", BF3_SHAPES, ids=lambda s: "ppw%d_pxt%d_ks%d_wco%d" % s)

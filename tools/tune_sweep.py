@@ -13,8 +13,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import golden_inputs as gi  # noqa: E402
 import iaf_amd  # noqa: E402
-
-SHAPES = [(4, 1, 1), (4, 1, 2), (2, 2, 1), (2, 2, 2), (2, 1, 2), (2, 1, 4), (1, 1, 4), (1, 2, 2)]
+from iaf_amd.build import SHAPES  # noqa: E402
 
 
 def main():
