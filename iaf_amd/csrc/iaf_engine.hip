@@ -2704,6 +2704,62 @@ extern "C" int iaf_adamax_ema_step(float* var, const float* grad, float* slot_m,
     return (int)hipGetLastError();
 }
 
+// the guarded step: a skip counter in mapped host memory (read without synchronising), the scan, the gated update
+struct iaf_skip_counter {
+    unsigned* host = nullptr;
+    unsigned* dev = nullptr;
+};
+
+extern "C" int iaf_skip_counter_create(iaf_skip_counter_t** out) {
+    if (!out) return IAF_ERR_NULL;
+    *out = nullptr;
+    iaf_skip_counter_t* c = new iaf_skip_counter_t();
+    if (hipHostMalloc((void**)&c->host, 64, hipHostMallocMapped) != hipSuccess) { delete c; return (int)hipErrorOutOfMemory; }
+    *(volatile unsigned*)c->host = 0u;
+    if (hipHostGetDevicePointer((void**)&c->dev, c->host, 0) != hipSuccess) {
+        (void)hipHostFree(c->host);
+        delete c;
+        return (int)hipErrorOutOfMemory;
+    }
+    *out = c;
+    return IAF_OK;
+}
+
+extern "C" int iaf_skip_counter_read(const iaf_skip_counter_t* c, unsigned* count) {
+    if (!c || !count) return IAF_ERR_NULL;
+    *count = *(volatile const unsigned*)c->host;
+    return IAF_OK;
+}
+
+extern "C" int iaf_skip_counter_destroy(iaf_skip_counter_t* c) {
+    if (!c) return IAF_OK;
+    if (c->host) (void)hipHostFree(c->host);
+    delete c;
+    return IAF_OK;
+}
+
+extern "C" int iaf_nonfinite_scan(const float* buf, size_t n, const float* extra, int n_extra, unsigned* guard, void* stream) {
+    if (!guard || (n && !buf) || n_extra < 0 || (n_extra && !extra)) return IAF_ERR_NULL;
+    if (n_extra > 256) return IAF_ERR_SHAPE;                 // (the extras are read by the first workgroup's lanes)
+    if (((uintptr_t)guard & 7) != 0) return IAF_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n4 = ((uintptr_t)buf & 15) == 0 ? n / 4 : 0;
+    hipLaunchKernelGGL(iaf_nonfinite_scan_kernel, ew_grid((n4 ? n4 : n) > (size_t)n_extra ? (n4 ? n4 : n) : (size_t)n_extra), dim3(256), 0, st, buf,
+                       n4, n, extra, n_extra, guard);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_adamax_ema_step_guarded(float* var, const float* grad, float* slot_m, float* slot_v, float* ema, size_t n,
+                                           float lr, float beta1, float beta2, float eps, float ema_decay, float grad_scale,
+                                           const unsigned* guard, iaf_skip_counter_t* skips, void* stream) {
+    if (!var || !grad || !slot_m || !slot_v || !guard || !skips) return IAF_ERR_NULL;
+    const bool al = (((uintptr_t)var | (uintptr_t)grad | (uintptr_t)slot_m | (uintptr_t)slot_v | (uintptr_t)ema) & 15) == 0;
+    const size_t n4 = al ? n / 4 : 0;
+    hipLaunchKernelGGL(iaf_adamax_ema_guarded_kernel, ew_grid(n4 ? n4 : n), dim3(256), 0, (hipStream_t)stream, var, grad, slot_m,
+                       slot_v, ema, n4, n, lr, beta1, beta2, eps, ema_decay, grad_scale, guard, skips->dev);
+    return (int)hipGetLastError();
+}
+
 extern "C" int iaf_layer_work(const iaf_stack_t* s, int layer, int B, int H, int W, double* live_flops,
                               double* dense_flops, double* bytes) {
     if (!s) return IAF_ERR_NULL;

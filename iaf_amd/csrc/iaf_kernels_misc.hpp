@@ -278,6 +278,72 @@ __global__ __launch_bounds__(256) void iaf_adamax_ema_kernel(float* __restrict__
     }
 }
 
+// The guard of a training step: guard[0] = 1 if NaN or +-inf is anywhere in the (all-reduced) flat gradient or in `extra` (the
+// step's objective), else 0.  One HBM-bound read of the buffer; non-finite = exponent field all ones, tested on the bits so that
+// no fast-math setting can fold it away.  Per workgroup one combine (the waves' ballots) and ONE device-scope atomic on guard[1]:
+// the low 16 bits count the workgroups that have arrived, the high bits the ones that saw a non-finite value.  The last workgroup
+// to arrive writes the verdict to guard[0] and puts guard[1] back to 0 -- every scan writes its own verdict and leaves the word
+// as it found it, so nothing has to clear the guard between calls or graph replays (grids <= 2048 workgroups: ew_grid).
+__device__ __forceinline__ bool iaf_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+__global__ __launch_bounds__(256) void iaf_nonfinite_scan_kernel(const float* __restrict__ buf, size_t n4, size_t n,
+                                                                const float* __restrict__ extra, int n_extra, unsigned* guard) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    bool bad = false;
+    for (size_t i = t; i < n4; i += stride) {
+        const f32x4 v = ((const f32x4*)buf)[i];
+        bad |= iaf_nonfinite(v[0]) | iaf_nonfinite(v[1]) | iaf_nonfinite(v[2]) | iaf_nonfinite(v[3]);
+    }
+    for (size_t i = 4 * n4 + t; i < n; i += stride) bad |= iaf_nonfinite(buf[i]);      // tail
+    if (t < (size_t)n_extra) bad |= iaf_nonfinite(extra[t]);
+    bad = __syncthreads_or(bad) != 0;                                                    // the workgroup's verdict
+    if (threadIdx.x == 0) {
+        const unsigned mine = 1u + (bad ? 0x10000u : 0u);
+        const unsigned total = __hip_atomic_fetch_add(guard + 1, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + mine;
+        if ((total & 0xffffu) == gridDim.x) {                                               // the last workgroup
+            __hip_atomic_store(guard, (total >> 16) ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(guard + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// iaf_adamax_ema_kernel behind the guard: *guard == 0 -> the same arithmetic, statement for statement (bit-identical results);
+// *guard != 0 -> no store to var, the slots or ema, and one lane adds 1 to the skip counter (mapped host memory)
+__global__ __launch_bounds__(256) void iaf_adamax_ema_guarded_kernel(float* __restrict__ var, const float* __restrict__ grad,
+                                                                    float* __restrict__ slot_m, float* __restrict__ slot_v,
+                                                                    float* __restrict__ ema, size_t n4, size_t n, float lr, float beta1,
+                                                                    float beta2, float eps, float ema_decay, float grad_scale,
+                                                                    const unsigned* guard, unsigned* skips) {
+    if (__hip_atomic_load(guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_fetch_add(skips, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+    }
+    auto upd = [&](float& w, float g, float& m, float& v, float& e) {
+        g *= grad_scale;
+        v = beta1 * v + (1.f - beta1) * g;                    // adamax.py:50
+        m = fmaxf(beta2 * m + eps, fabsf(g));                 // adamax.py:52
+        w -= lr * (v / m);                                    // adamax.py:53-55
+        e -= (1.f - ema_decay) * (e - w);                     // ExponentialMovingAverage.apply
+    };
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
+        f32x4 w = ((f32x4*)var)[i], g = ((const f32x4*)grad)[i], m = ((f32x4*)slot_m)[i], v = ((f32x4*)slot_v)[i];
+        f32x4 e = ema ? ((f32x4*)ema)[i] : w;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float wr_ = w[r], mr = m[r], vr = v[r], er = e[r];
+            upd(wr_, g[r], mr, vr, er);
+            w[r] = wr_; m[r] = mr; v[r] = vr; e[r] = er;
+        }
+        ((f32x4*)var)[i] = w; ((f32x4*)slot_m)[i] = m; ((f32x4*)slot_v)[i] = v;
+        if (ema) ((f32x4*)ema)[i] = e;
+    }
+    for (size_t i = 4 * n4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += stride) {   // tail
+        float e = ema ? ema[i] : var[i];
+        upd(var[i], grad[i], slot_m[i], slot_v[i], e);
+        if (ema) ema[i] = e;
+    }
+}
+
 // streaming logsumexp over k importance weights per image: one wave per image
 __global__ __launch_bounds__(256) void iaf_lb_update_kernel(float* run_max, float* run_sum, const float* log_pxz,
                                                            const float* sum_kl, int n, int kc) {

@@ -188,6 +188,18 @@ class OverlappedGradReduce(object):
         else:
             self.works.append(dist.all_reduce(self.flat.grads[lo:hi], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
+    def reduce_tensor(self, t):
+        """all-reduce(sum) in place of another small buffer `t` (e.g. a status word every rank must agree on) on the same exchange
+        path as the buckets, issued at this point of the compute stream and joined by wait() like them"""
+        if not self.active:
+            return
+        if self.comm is not None:
+            self.xstream.wait_stream(torch.cuda.current_stream())
+            self.comm.all_reduce_sum_(t, stream=self.xstream)
+            self._pending = True
+        else:
+            self.works.append(dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+
     def wait(self):
         if self._pending:
             torch.cuda.current_stream().wait_stream(self.xstream)       # the optimiser runs behind the last bucket

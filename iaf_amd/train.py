@@ -1,0 +1,285 @@
+"""TrainStep -- one data-parallel training step of CVAE1 (tf_train.py:124-159) with a guard: the update is applied only if the
+step's all-reduced gradients and objective are finite.
+
+The step is the one bench.py --train --model times: every weight norm re-derived (CVAE1.prepare_weights), forward and backward
+(CVAE1.fb_begin / fb_segment) into ONE flat gradient buffer laid out in completion order (parallel.FlatParams), bucket i's
+all-reduce(sum) issued behind backward segment i (parallel.OverlappedGradReduce), the join, then
+  - the guard scan (iaf_nonfinite_scan) of the reduced flat gradient and of a status word that went through the same reduce (the
+    sum of the ranks' objectives: one rank's non-finite objective makes it non-finite on every rank), and
+  - the gated Adamax / EMA (iaf_adamax_ema_step_guarded, grad_scale 1/world): bit-identical to FlatParams.adamax_ema_step when
+    the guard is clear; when it is raised nothing moves and a counter in mapped host memory counts the skip.
+Every rank scans the same reduced numbers, so every rank takes the same decision.  A skipped batch is dropped (as
+torch.amp.GradScaler does), not recomputed.
+
+Why a step goes non-finite on a model the fp32 reference trains through: an operand beyond 65504 in a launch on two fp16 planes
+(the default arithmetic of the one-launch step and the forward convs) makes that launch's outputs inf / NaN; its stack or conv
+raises a range word, and only its NEXT eager call reports IAF_ERR_RANGE and moves it to bf16 planes (include/iaf_hip.h).  A
+replayed hipGraph runs no host code and would keep the fp16-plane launch forever.  So at the first call after the host has seen
+the skip counter rise, every object whose range word is newly set is moved through that existing protocol (compute-only eager
+passes on the call's inputs, no collective, no update) and the graph is captured again on the same stream; from then on the
+step runs where it did not overflow."""
+import ctypes
+import math
+import warnings
+
+import torch
+import torch.distributed as dist
+
+from . import _capi
+from .parallel import FlatParams, OverlappedGradReduce
+
+# the errors an object reports once, at its next eager call, about an EARLIER launch whose outputs carry inf / NaN; the object has
+# switched kernels and the call can be repeated
+_SWITCHED = (_capi.RangeError, _capi.ExchangeError)
+
+
+class _SkipCounter(object):
+    """iaf_skip_counter_t: the number of updates the gated kernel skipped, in mapped host memory"""
+
+    def __init__(self):
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib().iaf_skip_counter_create(ctypes.byref(h)))
+        self._h = h
+
+    def read(self):
+        """the count as far as the device has got (no synchronisation)"""
+        c = ctypes.c_uint()
+        _capi.check(_capi.lib().iaf_skip_counter_read(self._h, ctypes.byref(c)))
+        return c.value
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _capi.destroy("iaf_skip_counter_destroy", self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _range_objects(model):
+    """the stacks and convs of a CVAE1 that keep a range word (an object without `layers` has none)"""
+    out = []
+    for level in getattr(model, "layers", []):
+        for layer in level:
+            out.append(layer.posterior.stack)
+            out.extend(layer.convs())
+    return out
+
+
+class TrainStep(object):
+    """ts = TrainStep(model, lr); obj = ts(x, noise) per batch.
+
+    model: a CVAE1 after set_training(True) and load(params).  The constructor lays its variables out in ONE flat buffer in
+    model.completion_order() (ts.flat: params, grads, slots, EMA; the model is re-loaded with the views of ts.flat.p), cuts the
+    backward into `n_buckets` gradient buckets (model.set_grad_buckets) and sets up their all-reduce (through `comm`, a
+    parallel.RcclComm, when one is given; else torch.distributed's default group when it has more than one rank).
+    lr, beta1, beta2, eps, ema_decay: Adamax and the EMA (tf_utils/adamax.py:40-56, tf_train.py:146-159).
+    graph=True captures the whole step as one hipGraph on a stream of its own (segments, forked all-reduces, join, scan, gated
+    update); if the runtime refuses the capture, the step runs as eager launches (ts.graph_refused says why).
+
+    ts(x, noise) enqueues one step on the current stream and returns the device objective [1] (graph mode: x and noise are first
+    copied into the graph's static inputs -- same shapes every call -- and the returned tensor is overwritten by the next step).
+    It does not synchronise.  ts.flat.g holds the step's all-reduced gradients afterwards.  ts.skipped synchronises and returns the
+    number of skipped updates so far."""
+
+    def __init__(self, model, lr, n_buckets=1, comm=None, graph=True, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.999):
+        if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0:
+            raise ValueError("lr must be a positive finite number, got %r" % (lr,))
+        if isinstance(n_buckets, bool) or not isinstance(n_buckets, int) or n_buckets < 1:
+            raise ValueError("n_buckets must be a positive int, got %r" % (n_buckets,))
+        if not isinstance(graph, bool):
+            raise ValueError("graph must be True or False, got %r" % (graph,))
+        for nm, v in (("beta1", beta1), ("beta2", beta2), ("ema_decay", ema_decay)):
+            if not (isinstance(v, (int, float)) and 0.0 <= v < 1.0):
+                raise ValueError("%s must lie in [0, 1), got %r" % (nm, v))
+        if not (isinstance(eps, (int, float)) and math.isfinite(eps) and eps >= 0):
+            raise ValueError("eps must be a finite number >= 0, got %r" % (eps,))
+        if getattr(model, "params", None) is None:
+            raise RuntimeError("TrainStep: model.set_training(True), then model.load(params), first")
+        self.model, self.lr = model, float(lr)
+        self._hyper = (float(beta1), float(beta2), float(eps), float(ema_decay))
+        self.flat = FlatParams({k: model.params[k] for k in model.completion_order()})
+        self.on_device = self.flat.params.is_cuda
+        if graph and not self.on_device:
+            raise ValueError("TrainStep: graph=True needs device parameters")
+        model.load(self.flat.p)
+        names = model.set_grad_buckets(n_buckets)
+        self.n_buckets = len(names)
+        self.red = OverlappedGradReduce(self.flat, OverlappedGradReduce.bounds_from_groups(self.flat, names), force=comm is not None,
+                                        comm=comm)
+        self.world = 1
+        if self.red.active:
+            self.world = int(getattr(self.red.comm, "world", 0) or dist.get_world_size())
+        dev = self.flat.params.device
+        # [0]: the step's objective, summed over the ranks by the same exchange as the gradients (the rest: 16-byte padding)
+        self._status = torch.zeros(4, dtype=torch.float32, device=dev)
+        if self.on_device:
+            self._guard = torch.zeros(4, dtype=torch.int32, device=dev)
+            self._skips = _SkipCounter()
+        self._host_skips = 0
+        self._acted = 0                   # the count at the last recovery
+        self._aborted = False             # an eager step could not finish on this rank (an object switched kernels in the middle)
+        self._seen = set()                # range objects already moved to bf16 planes
+        self._objects = _range_objects(model)
+        self.use_graph = graph
+        self.graph_refused = None
+        self.captures = 0
+        self._graph = None
+        self._static = None
+        self._stream = torch.cuda.Stream(device=dev) if graph else None
+
+    # -- the step's launches ------------------------------------------------------------------------------------------------------
+    def _compute(self, x, noise):
+        """forward and backward only: no collective, no update (the passes that move objects whose range word is set)"""
+        self.model.prepare_weights()
+        self.model.fb_begin(x, noise, grads=self.flat.g)
+        for i in range(self.n_buckets):
+            self.model.fb_segment(i)
+
+    def _enqueue(self, x, noise):
+        """one whole step on the current stream; returns the objective"""
+        m, red, flat = self.model, self.red, self.flat
+        sent, status_sent = 0, False
+        try:
+            m.prepare_weights()
+            obj = m.fb_begin(x, noise, grads=flat.g)["obj"]
+            self._status[:1].copy_(obj.reshape(1))
+            red.reduce_tensor(self._status)
+            status_sent = True
+            for i in range(self.n_buckets):
+                m.fb_segment(i)
+                red.reduce(i)
+                sent = i + 1
+        except _SWITCHED:
+            if self.on_device and torch.cuda.is_current_stream_capturing():
+                raise
+            # An object reported a failed EARLIER launch and switched kernels: this rank cannot finish the step's compute.  Every rank
+            # still issues the same collectives, and every rank must skip: the buckets not yet sent (and the status, if not yet sent)
+            # go out as NaN.  The next call moves what else needs moving before it enqueues anything.
+            self._aborted = True
+            if not status_sent:
+                self._status.fill_(float("nan"))
+                red.reduce_tensor(self._status)
+            flat.grads[red.bounds[sent][0]:].fill_(float("nan"))
+            for i in range(sent, self.n_buckets):
+                red.reduce(i)
+            obj = torch.full((1,), float("nan"), dtype=torch.float32, device=flat.params.device)
+        red.wait()
+        self._update()
+        return obj
+
+    def _update(self):
+        flat, (b1, b2, eps, decay) = self.flat, self._hyper
+        if self.on_device:
+            lib = _capi.lib()
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _capi.check(lib.iaf_nonfinite_scan(ptr(flat.grads), flat.grads.numel(), ptr(self._status), 1, ptr(self._guard), st))
+            _capi.check(lib.iaf_adamax_ema_step_guarded(ptr(flat.params), ptr(flat.grads), ptr(flat.slot_m), ptr(flat.slot_v),
+                                                        ptr(flat.ema), flat.params.numel(), self.lr, b1, b2, eps, decay,
+                                                        1.0 / self.world, ptr(self._guard), self._skips._h, st))
+            # (raw-pointer writes: tell torch, as FlatParams.adamax_ema_step does)
+            torch.autograd.graph.increment_version((flat.params, flat.ema, flat.slot_m, flat.slot_v))
+        else:        # host replicas: the same decision with torch ops
+            if bool(torch.isfinite(flat.grads).all()) and bool(torch.isfinite(self._status[:1]).all()):
+                flat.adamax_ema_step(self.lr, world=self.world, beta1=b1, beta2=b2, eps=eps, ema_decay=decay)
+            else:
+                self._host_skips += 1
+
+    # -- recovery after a skip --------------------------------------------------------------------------------------------------
+    def _count(self):
+        return self._skips.read() if self.on_device else self._host_skips
+
+    def _must_move(self):
+        """True if objects must be moved to bf16 planes (and the graph captured again) before this call's step"""
+        if not self._aborted and self._count() <= self._acted:
+            return False
+        if self.on_device:
+            torch.cuda.synchronize()
+        self._acted = self._count()
+        flagged = {i for i, o in enumerate(self._objects) if o.range_errors()}
+        new = flagged - self._seen
+        self._seen |= flagged
+        moved, self._aborted = self._aborted or bool(new), False
+        return moved
+
+    def _move(self, x, noise):
+        """Compute-only eager passes on (x, noise) until two in a row report nothing: each report moves one object to bf16 planes
+        (existing protocol), and a pass on the new kernels can overflow further down, which the pass after it reports."""
+        clean, limit = 0, 2 * len(self._objects) + 4
+        for _ in range(limit):
+            if self.on_device:
+                torch.cuda.synchronize()
+            try:
+                self._compute(x, noise)
+                clean += 1
+            except _SWITCHED:
+                clean = 0
+            if clean == 2:
+                if self.on_device:
+                    torch.cuda.synchronize()
+                return
+        raise _capi.IafHipError("TrainStep: objects kept reporting range / exchange failures after %d passes" % limit)
+
+    def _capture(self):
+        self._graph = None
+        x, noise = self._static
+        s = self._stream
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for attempt in range(2):
+                self._move(x, noise)         # (also the warm-up: workspaces, exchange sets and launch caches exist before the capture)
+                g = torch.cuda.CUDAGraph()
+                try:
+                    with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
+                        obj = self._enqueue(x, noise)
+                except _SWITCHED:
+                    torch.cuda.synchronize()
+                    continue
+                except Exception as e:       # noqa: BLE001
+                    self.graph_refused = (str(e).splitlines() or [""])[0]
+                    warnings.warn("TrainStep: the runtime refused to capture the step (%s): eager launches" % self.graph_refused,
+                                  RuntimeWarning, stacklevel=3)
+                    torch.cuda.synchronize()
+                    return
+                self._graph, self._sobj = g, obj
+                self.captures += 1
+                break
+        torch.cuda.current_stream().wait_stream(s)
+        if self._graph is None and self.graph_refused is None:
+            raise _capi.IafHipError("TrainStep: the capture kept meeting objects that switch kernels")
+
+    # -- public ---------------------------------------------------------------------------------------------------------------------
+    def __call__(self, x, noise):
+        moved = self._must_move()
+        if self.use_graph and self.graph_refused is None:
+            if self._static is None:
+                self._static = (x.clone(), [e.clone() for e in noise])
+                moved = True
+            else:
+                sx, sn = self._static
+                if x.shape != sx.shape or x.dtype != sx.dtype or len(noise) != len(sn) or any(a.shape != b.shape for a, b in zip(noise, sn)):
+                    raise ValueError("TrainStep(graph=True): x and noise must keep the shapes of the first call")
+                sx.copy_(x)
+                for a, b in zip(sn, noise):
+                    a.copy_(b)
+            if moved:
+                self._capture()
+            if self._graph is not None:
+                self._graph.replay()
+                return self._sobj
+        if moved:
+            self._move(x, noise)
+        return self._enqueue(x, noise)
+
+    @property
+    def skipped(self):
+        """the number of updates skipped so far (synchronises the device)"""
+        if self.on_device:
+            torch.cuda.synchronize()
+        return self._count()
+
+    @property
+    def graphed(self):
+        """True if the steps replay a captured hipGraph"""
+        return self._graph is not None

@@ -207,6 +207,32 @@ const char* iaf_comm_library(void);
 int iaf_adamax_ema_step(float* var, const float* grad, float* slot_m, float* slot_v, float* ema, size_t n, float lr,
                         float beta1, float beta2, float eps, float ema_decay, float grad_scale, void* stream);
 
+/* The guarded optimiser step: an update is applied only if the step's gradients and objective are finite.
+ *   iaf_nonfinite_scan writes guard[0] = 1 if any of buf[0..n) or extra[0..n_extra) (n_extra <= 256: the objective, a status
+ *   word) is NaN or +-inf -- an exponent field of all ones, tested on the bits -- else guard[0] = 0.  The largest finite float and
+ *   subnormals are finite.  guard: 4 unsigned device words, 8-byte aligned, ZERO when first used; words 1..3 are the scan's
+ *   arrival count, which the scan's last workgroup puts back to 0.  Every scan writes its own verdict, so no host write or memset
+ *   is needed between calls or between replays of a captured hipGraph.  One scan at a time per guard.
+ *   iaf_adamax_ema_step_guarded is iaf_adamax_ema_step (bit-identical results) while guard[0] is 0; with guard[0] set it writes
+ *   nothing to var, the slots or ema (the reference's Adamax keeps no step count, tf_utils/adamax.py:40-56: a skipped step
+ *   moves nothing) and adds 1 to the skip counter.  The counter lives in mapped host memory: iaf_skip_counter_read returns
+ *   it without synchronising (the updates enqueued so far may not have run yet).
+ * The decision is per call: each scan judges the buffers as they are when it runs.  For data-parallel training, scan the
+ * all-reduced gradient and a status word that went through the same reduce (iaf_amd/train.py: the sum of the ranks'
+ * objectives): every rank then decides the same.  A skipped step on two fp16 planes (IAF_PRECISION_F16X2) has raised the
+ * range word of the stack or conv that overflowed; only the NEXT eager call on that object reports IAF_ERR_RANGE and moves it
+ * to bf16 planes.  Replays of a captured hipGraph never run that host-side check, exactly as for IAF_ERR_EXCHANGE: the graph
+ * keeps the fp16-plane launch (and keeps being skipped) until the object has been switched by an eager call AND the graph is
+ * captured again -- read the counter between replays to know when. */
+typedef struct iaf_skip_counter iaf_skip_counter_t;
+int iaf_skip_counter_create(iaf_skip_counter_t** out);
+int iaf_skip_counter_read(const iaf_skip_counter_t* c, unsigned* count);
+int iaf_skip_counter_destroy(iaf_skip_counter_t* c);
+int iaf_nonfinite_scan(const float* buf, size_t n, const float* extra, int n_extra, unsigned* guard, void* stream);
+int iaf_adamax_ema_step_guarded(float* var, const float* grad, float* slot_m, float* slot_v, float* ema, size_t n, float lr,
+                                float beta1, float beta2, float eps, float ema_decay, float grad_scale, const unsigned* guard,
+                                iaf_skip_counter_t* skips, void* stream);
+
 /* Full posterior block, tf_train.py:56-85 (mode "train"): everything between down_conv1 and
  * the concat, i.e. posterior sample, logqs, IAF step, log-det accumulation, prior logps, KL and
  * free bits.  All [B,n_z,H,W] inputs NCHW; up_context/down_context [B,n_h,H,W]; eps is the

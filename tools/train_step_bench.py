@@ -1,0 +1,137 @@
+#!/usr/bin/env python
+"""GPU dev tool: what the guard of iaf_amd.TrainStep costs.  At the BASELINE geometry (B = 32, z 32, h 160, depths [10, 10], 32x32
+images, seeded weights, launch shapes autotuned as bench.py --train --model does) it times, in alternation (median over rounds of
+back-to-back replays between HIP events on the current stream):
+  guarded     the hipGraph of TrainStep(model, lr) replayed: prep, forward, backward, reduce, join, guard scan, gated Adamax / EMA
+  unguarded   the same step captured on the same stream with FlatParams.adamax_ema_step in place of scan + gated update
+  call        ts(x, noise): the guarded replay plus the copies of x and noise into the graph's static inputs
+  scan_us     iaf_nonfinite_scan of the flat gradient alone (50 back-to-back launches)
+then forces one re-capture of the guarded step (the path a skip takes after an object moved to bf16 planes) and times it again: a
+re-captured step that is slower than the first capture by more than 2 % is reported as probably running the recomputing one-launch
+step instead of the halo exchange (the exchange sets of a stream stay marked as captured: include/iaf_hip.h).
+Prints one JSON line."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+
+def timed(fn, reps):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--num-blocks", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=10)
+    args = ap.parse_args()
+    import torch
+    import golden_inputs as gi
+    import iaf_amd
+    from iaf_amd import _capi
+    B, zs, hs, nb = args.batch, 32, 160, args.num_blocks
+    gi.MODEL_CASES["train_step_bench"] = (B, 1, zs, hs, 2, nb, 32, 0.25)
+    c = gi.model_case_inputs("train_step_bench")
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    model = iaf_amd.CVAE1(z_size=zs, h_size=hs, kl_min=0.25, depth=2, num_blocks=nb, k=1, image_size=32)
+    model.set_training(True)
+    model.load({k: dev(v) for k, v in c["params"].items()})
+    rng = np.random.RandomState(99)
+    x = torch.from_numpy(rng.randint(0, 256, size=(B, 3, 32, 32)).astype(np.uint8)).cuda()
+    noise = [dev(rng.standard_normal(e.shape)) for e in c["noise"]]
+    lr = 1e-4
+    ts = iaf_amd.TrainStep(model, lr, graph=True)
+    flat, red = ts.flat, ts.red
+    for tune in (True, False):                          # launch-shape search of the plain convs (bench.py --train --model does the same)
+        model.prepare_weights()
+        model.fb_begin(x, noise, grads=flat.g, autotune=tune)
+        for i in range(ts.n_buckets):
+            model.fb_segment(i)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ts(x, noise)
+    torch.cuda.synchronize()
+    first_call_s = time.perf_counter() - t0
+    if not ts.graphed:
+        raise SystemExit("train_step_bench: the step was not captured (%s)" % ts.graph_refused)
+
+    def plain_step():
+        model.prepare_weights()
+        model.fb_begin(x, noise, grads=flat.g)
+        for i in range(ts.n_buckets):
+            model.fb_segment(i)
+            red.reduce(i)
+        red.wait()
+        flat.adamax_ema_step(lr, world=ts.world)
+
+    s = ts._stream                                      # the guarded step's capture stream: the two graphs share its exchange sets
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        plain_step()
+        torch.cuda.synchronize()
+        g_plain = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g_plain, stream=s, capture_error_mode="thread_local"):
+            plain_step()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    call = lambda: ts(x, noise)                          # the public call: also copies x and noise into the graph's static inputs
+    guarded = lambda: ts._graph.replay()                 # the guarded step alone, like for like with the unguarded replay
+    for _ in range(3):
+        call()
+        g_plain.replay()
+    tg, tp, tc = [], [], []
+    for _ in range(args.rounds):
+        tg.append(timed(guarded, args.reps))
+        tp.append(timed(g_plain.replay, args.reps))
+        tc.append(timed(call, args.reps))
+    mg, mp, mc = float(np.median(tg)), float(np.median(tp)), float(np.median(tc))
+    lib = _capi.lib()
+    st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    guard = torch.zeros(4, dtype=torch.int32, device="cuda")
+    scan = lambda: _capi.check(lib.iaf_nonfinite_scan(P(flat.grads), flat.grads.numel(), P(ts._status), 1, P(guard), st()))
+    scan()
+    scan_us = 1e3 * float(np.median([timed(scan, 50) for _ in range(5)]))
+    # one re-capture of the guarded step, as after a skip that moved an object to bf16 planes
+    t0 = time.perf_counter()
+    ts._capture()
+    torch.cuda.synchronize()
+    recapture_s = time.perf_counter() - t0
+    for _ in range(3):
+        call()
+    guarded = lambda: ts._graph.replay()
+    tr = [timed(guarded, args.reps) for _ in range(args.rounds)]
+    mr = float(np.median(tr))
+    skipped = ts.skipped
+    obj = float(ts._sobj.item())
+    print(json.dumps({
+        "tool": "train_step_bench", "B": B, "z": zs, "h": hs, "depths": [nb, nb], "params": int(flat.params.numel()),
+        "flat_mb": 4e-6 * flat.params.numel(),
+        "guarded_ms": mg, "unguarded_ms": mp, "guard_overhead_ms": mg - mp, "guard_overhead_frac": (mg - mp) / mp,
+        "scan_us": scan_us, "scan_gbs": 4 * flat.grads.numel() / (scan_us * 1e-6) / 1e9,
+        "call_ms": mc, "call_repeats_ms": tc, "guarded_repeats_ms": tg, "unguarded_repeats_ms": tp,
+        "first_call_s": first_call_s, "recapture_s": recapture_s, "recaptured_ms": mr, "recaptured_repeats_ms": tr,
+        "recaptured_over_first": mr / mg, "recaptured_probably_recomputes_halo_rows": bool(mr > 1.02 * mg),
+        "captures": ts.captures, "skipped": skipped, "obj_last": obj,
+        "timing": "median of %d rounds of %d back-to-back steps between HIP events, guarded and unguarded in alternation" % (args.rounds, args.reps)}))
+
+
+if __name__ == "__main__":
+    main()
