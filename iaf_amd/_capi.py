@@ -188,6 +188,13 @@ SIGNATURES = {
                                             ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_int),
                                             ctypes.POINTER(ctypes.c_float)]),
     "iaf_conv3x3_set_tuning": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4),
+    "iaf_rng_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_uint64]),
+    "iaf_rng_destroy": (ctypes.c_int, [_vp]),
+    "iaf_rng_fill_normal": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint),
+                                           ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_int, _vp]),
+    "iaf_rng_seek": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
+    "iaf_rng_skip": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
+    "iaf_rng_tell": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), _vp]),
     "iaf_conv3x3_work": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 2),
 }
 

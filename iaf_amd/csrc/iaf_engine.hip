@@ -31,6 +31,7 @@
 //   iaf_kernels_backward.hpp  weight gradient, weight-norm backward, staging, posterior-block backward pieces
 //   iaf_kernels_generic.hpp   direct-conv fallback for channel counts outside the MFMA path
 //   iaf_kernels_resample.hpp  2x resampling and the deconv2d weight prep (downsampling IAFLayer)
+//   iaf_kernels_rng.hpp       the device noise source: Philox4x32-10 normals for a list of tensors in one launch
 //   (this file)               stack object, launch logic, C ABI of the masked stack, forward / inverse / training
 //   iaf_conv3x3_host.hpp      C ABI of the plain and single masked 3x3 convs, init, likelihood
 //   iaf_model_edge.hpp        the two ends of the model around the layer stack (CVAE1._forward: x_enc, h_top, x_dec, obj / loss)
@@ -62,6 +63,7 @@
 #include "iaf_kernels_backward.hpp"
 #include "iaf_kernels_generic.hpp"
 #include "iaf_kernels_resample.hpp"
+#include "iaf_kernels_rng.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side: stack object
@@ -2758,6 +2760,93 @@ extern "C" int iaf_adamax_ema_step_guarded(float* var, const float* grad, float*
     hipLaunchKernelGGL(iaf_adamax_ema_guarded_kernel, ew_grid(n4 ? n4 : n), dim3(256), 0, (hipStream_t)stream, var, grad, slot_m,
                        slot_v, ema, n4, n, lr, beta1, beta2, eps, ema_decay, grad_scale, guard, skips->dev);
     return (int)hipGetLastError();
+}
+
+// the device noise source (iaf_kernels_rng.hpp): the seed lives here, the 64-bit step counter in device memory, where the fill launch
+// reads it and a one-thread launch behind it advances it -- a replayed hipGraph draws fresh noise with no host code in between
+struct iaf_rng {
+    unsigned long long seed = 0;
+    unsigned long long* d_step = nullptr;
+};
+
+extern "C" int iaf_rng_create(iaf_rng_t** out, uint64_t seed) {
+    if (!out) return IAF_ERR_NULL;
+    *out = nullptr;
+    iaf_rng_t* r = new (std::nothrow) iaf_rng_t();
+    if (!r) return (int)hipErrorOutOfMemory;
+    r->seed = seed;
+    hipError_t e = hipMalloc((void**)&r->d_step, 64);
+    if (e == hipSuccess) e = hipMemset(r->d_step, 0, 64);
+    if (e != hipSuccess) {
+        if (r->d_step) (void)hipFree(r->d_step);
+        delete r;
+        return (int)e;
+    }
+    *out = r;
+    return IAF_OK;
+}
+
+extern "C" int iaf_rng_destroy(iaf_rng_t* r) {
+    if (!r) return IAF_OK;
+    if (r->d_step) (void)hipFree(r->d_step);
+    delete r;
+    return IAF_OK;
+}
+
+extern "C" int iaf_rng_fill_normal(iaf_rng_t* r, float* const* outs, const size_t* counts, const unsigned* substreams,
+                                   const float* scales, int n, int advance, void* stream) {
+    if (!r) return IAF_ERR_NULL;
+    if (n < 1 || n > IAF_RNG_MAX_TENSORS) return IAF_ERR_SHAPE;
+    if (!outs || !counts || !substreams) return IAF_ERR_NULL;
+    IafRngTable T;
+    memset(&T, 0, sizeof(T));
+    unsigned blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!outs[i]) return IAF_ERR_NULL;
+        if (counts[i] == 0 || (unsigned long long)counts[i] > (1ull << 34)) return IAF_ERR_SHAPE;
+        if ((uintptr_t)outs[i] & 3) return IAF_ERR_WORKSPACE;
+        const unsigned long long pieces = ((unsigned long long)counts[i] + 3) / 4, nb = (pieces + 255) / 256;
+        blocks += (unsigned)(nb < IAF_RNG_MAX_BLOCKS ? nb : IAF_RNG_MAX_BLOCKS);
+        T.out[i] = outs[i];
+        T.count[i] = counts[i];
+        T.sub[i] = substreams[i];
+        T.scale[i] = scales ? scales[i] : 1.f;
+        T.blk_end[i] = blocks;
+    }
+    T.n = n;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(iaf_rng_fill_kernel, dim3(blocks), dim3(256), 0, st, T, (const unsigned long long*)r->d_step,
+                       (unsigned)(r->seed & 0xffffffffull), (unsigned)(r->seed >> 32));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !advance) return (int)e;
+    hipLaunchKernelGGL(iaf_rng_step_kernel, dim3(1), dim3(1), 0, st, r->d_step, 1ull, 1);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_rng_seek(iaf_rng_t* r, uint64_t step, void* stream) {
+    if (!r) return IAF_ERR_NULL;
+    hipLaunchKernelGGL(iaf_rng_step_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, r->d_step, (unsigned long long)step, 0);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_rng_skip(iaf_rng_t* r, uint64_t steps, void* stream) {
+    if (!r) return IAF_ERR_NULL;
+    hipLaunchKernelGGL(iaf_rng_step_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, r->d_step, (unsigned long long)steps, 1);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_rng_tell(iaf_rng_t* r, uint64_t* step, void* stream) {
+    if (!r || !step) return IAF_ERR_NULL;
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st) (void)hipStreamIsCapturing(st, &cs);
+    if (cs == hipStreamCaptureStatusActive) return (int)hipErrorStreamCaptureUnsupported;
+    unsigned long long v = 0;
+    hipError_t e = hipMemcpyAsync(&v, r->d_step, sizeof(v), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    *step = v;
+    return IAF_OK;
 }
 
 extern "C" int iaf_layer_work(const iaf_stack_t* s, int layer, int B, int H, int W, double* live_flops,

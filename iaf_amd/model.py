@@ -197,8 +197,62 @@ class CVAE1(object):
         self.load(out)
         return x_out, out
 
-    def iw_eval(self, x, noise_passes):
-        """The k-sample importance-weighted bound of the whole model without materialising k samples at once (tf_train.py:168-170,218 with
+    # -- noise from the engine's own generator (iaf_amd.NoiseSource) instead of the caller ---------------------------------------------
+    def noise_shapes(self, B):
+        """Host bookkeeping: the shapes of forward()'s noise list for a batch of B images -- per layer in top-down order (eps_prior,
+        eps_post), B * k rows each."""
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError("B must be a positive int, got %r" % (B,))
+        return self._noise_shapes(B * self.k)
+
+    @staticmethod
+    def noise_shapes_for(rows, z_size, depth, num_blocks, image_size):
+        """Pure bookkeeping (no device, no instance): the shapes of the noise list of a depth x num_blocks model, `rows` rows each"""
+        out = []
+        for i in reversed(range(depth)):
+            Sl = image_size // 2 ** (i + 1)
+            out += [(rows, z_size, Sl, Sl)] * (2 * num_blocks)
+        return out
+
+    def _noise_shapes(self, rows):
+        return CVAE1.noise_shapes_for(rows, self.z_size, self.depth, self.num_blocks, self.image_size)
+
+    def draw_noise(self, B, source, which="both", out=None, temperature=1.0, advance=True, _rows=None):
+        """forward()'s noise list drawn by `source` (a NoiseSource) in ONE launch at its current step: which = "both", "posterior" (the
+        eps_post slots; what modes "train" and iw_eval read) or "prior" (the eps_prior slots; modes "init" / "sample", generate()) --
+        the slots not drawn are None.  A tensor's substream is source.substream_base + its index in the FULL list, so the posterior
+        noise does not depend on whether the prior noise is drawn with it.  temperature scales the prior entries (z = mean +
+        temperature * sd * eps).  out: a list from an earlier call with the same B and `which` -- its tensors are refilled.  No host
+        synchronisation: capturable."""
+        if which not in ("both", "posterior", "prior"):
+            raise ValueError("which must be 'both', 'posterior' or 'prior', got %r" % (which,))
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature):
+            raise ValueError("temperature must be a finite number, got %r" % (temperature,))
+        shapes = self.noise_shapes(B) if _rows is None else self._noise_shapes(_rows)      # (_rows: generate() does not apply k)
+        take = [i for i in range(len(shapes)) if which == "both" or (i % 2 == 1) == (which == "posterior")]
+        if out is None:
+            out = [None] * len(shapes)
+            for i in take:
+                out[i] = torch.empty(shapes[i], dtype=torch.float32, device=source.device)
+        elif (not isinstance(out, list) or len(out) != len(shapes)
+              or any((out[i] is None) != (i not in take) or (out[i] is not None and tuple(out[i].shape) != shapes[i]) for i in range(len(shapes)))):
+            raise ValueError("out: the list an earlier draw_noise(B=%d, which=%r) returned" % (B, which))
+        source.fill([out[i] for i in take], substreams=[source.substream_base + i for i in take],
+                    scales=[float(temperature) if i % 2 == 0 else 1.0 for i in take], advance=advance)
+        return out
+
+    def sample(self, B, source, temperature=1.0):
+        """B images from the prior with noise from `source` (one step of it): draw_noise(which="prior") + generate().  No host
+        synchronisation: capturable, and a replay draws fresh noise."""
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError("B must be a positive int, got %r" % (B,))
+        return self.generate(self.draw_noise(B, source, which="prior", temperature=temperature, _rows=B)[0::2])
+
+    def iw_eval(self, x, noise_passes=None, k=None, noise_source=None):
+        """With noise_source (a NoiseSource) and k: the k noise lists are drawn by the source, one step per pass, into ONE set of
+        buffers that every pass refills (memory does not grow with k) -- equal to passing the k lists draw_noise(which="posterior")
+        returns at those steps.  Otherwise noise_passes as below.
+        The k-sample importance-weighted bound of the whole model without materialising k samples at once (tf_train.py:168-170,218 with
         hps.k = len(noise_passes); BASELINE config 5 evaluates k = 10^4): one top-down pass with k = 1 per sample, the per-image terms
         log_pxz and sum-of-KL streamed into the running log-sum-exp (StreamingLowerBound).  The bottom-up pass -- image scaling, x_enc,
         every layer's up_conv1 / up_conv3 (tf_train.py:183-187) -- depends on x only: it runs ONCE and its products (qz_mean, qz_logsd,
@@ -206,7 +260,23 @@ class CVAE1(object):
         Returns the loss [1] = sum over images of -log (1/k) sum_s exp(log_pxz_s - kl_s); bits_per_dim(loss, B) as usual."""
         if self.k != 1:
             raise ValueError("iw_eval streams the samples: build the model with k = 1")
+        if (noise_passes is None) == (noise_source is None):
+            raise ValueError("iw_eval: either noise_passes or noise_source (with k)")
+        if noise_source is None:
+            if k is not None:
+                raise ValueError("iw_eval: k goes with noise_source (noise_passes carries its own length)")
+        elif isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError("iw_eval: k must be a positive int with noise_source, got %r" % (k,))
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise ValueError("x must be a contiguous uint8 [B,3,S,S] device tensor")
         B = int(x.shape[0])
+        if noise_source is not None:
+            def drawn():                  # one buffer set, refilled (one step of the source) per pass
+                buf = None
+                for _ in range(k):
+                    buf = self.draw_noise(B, noise_source, which="posterior", out=buf)
+                    yield buf
+            noise_passes = drawn()
         acc = StreamingLowerBound(B, x.device)
         xf = None
         for noise in noise_passes:

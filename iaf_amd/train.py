@@ -80,9 +80,17 @@ class TrainStep(object):
     ts(x, noise) enqueues one step on the current stream and returns the device objective [1] (graph mode: x and noise are first
     copied into the graph's static inputs -- same shapes every call -- and the returned tensor is overwritten by the next step).
     It does not synchronise.  ts.flat.g holds the step's all-reduced gradients afterwards.  ts.skipped synchronises and returns the
-    number of skipped updates so far."""
+    number of skipped updates so far.
 
-    def __init__(self, model, lr, n_buckets=1, comm=None, graph=True, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.999):
+    noise_source (a NoiseSource; device parameters only): ts(x) draws the step's posterior noise itself -- one launch into buffers the
+    step owns, the FIRST launch of the step, in graph mode inside the captured graph (the source's step counter lives in device memory:
+    every replay draws fresh noise and no launch or copy precedes the graph).  Call t (t = 0, 1, ...) uses step s0 + t of the source,
+    s0 being where the source stood at the first call, whatever was skipped or captured again: the compute-only passes (warm-up,
+    recovery) run on what the buffers hold and never advance the source.  ts(x, noise) with a list still works: that call runs as eager
+    launches on the list and moves the source on by one like any other call."""
+
+    def __init__(self, model, lr, n_buckets=1, comm=None, graph=True, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.999,
+                 noise_source=None):
         if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0:
             raise ValueError("lr must be a positive finite number, got %r" % (lr,))
         if isinstance(n_buckets, bool) or not isinstance(n_buckets, int) or n_buckets < 1:
@@ -102,6 +110,10 @@ class TrainStep(object):
         self.on_device = self.flat.params.is_cuda
         if graph and not self.on_device:
             raise ValueError("TrainStep: graph=True needs device parameters")
+        if noise_source is not None and not self.on_device:
+            raise ValueError("TrainStep: noise_source needs device parameters (host replicas take their noise from the caller)")
+        self.noise_source = noise_source
+        self._drawn = None                # the posterior noise buffers a source fills (forward()'s layout, None in the prior slots)
         model.load(self.flat.p)
         names = model.set_grad_buckets(n_buckets)
         self.n_buckets = len(names)
@@ -126,6 +138,7 @@ class TrainStep(object):
         self.captures = 0
         self._graph = None
         self._static = None
+        self._stale = False               # the captured graph must be captured again before its next replay
         self._stream = torch.cuda.Stream(device=dev) if graph else None
 
     # -- the step's launches ------------------------------------------------------------------------------------------------------
@@ -136,10 +149,13 @@ class TrainStep(object):
         for i in range(self.n_buckets):
             self.model.fb_segment(i)
 
-    def _enqueue(self, x, noise):
-        """one whole step on the current stream; returns the objective"""
+    def _enqueue(self, x, noise, draw=False):
+        """one whole step on the current stream; returns the objective.  draw: `noise` is the step's own buffer set, and the step's
+        first launch fills it from the noise source (one step of the source)"""
         m, red, flat = self.model, self.red, self.flat
         sent, status_sent = 0, False
+        if draw:
+            m.draw_noise(int(x.shape[0]), self.noise_source, which="posterior", out=noise)
         try:
             m.prepare_weights()
             obj = m.fb_begin(x, noise, grads=flat.g)["obj"]
@@ -232,7 +248,7 @@ class TrainStep(object):
                 g = torch.cuda.CUDAGraph()
                 try:
                     with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                        obj = self._enqueue(x, noise)
+                        obj = self._enqueue(x, noise, draw=self.noise_source is not None)
                 except _SWITCHED:
                     torch.cuda.synchronize()
                     continue
@@ -250,27 +266,51 @@ class TrainStep(object):
             raise _capi.IafHipError("TrainStep: the capture kept meeting objects that switch kernels")
 
     # -- public ---------------------------------------------------------------------------------------------------------------------
-    def __call__(self, x, noise):
-        moved = self._must_move()
-        if self.use_graph and self.graph_refused is None:
+    def _own_noise(self, x):
+        """the buffer set a noise source fills for batches like x; filled once WITHOUT advancing the source when it is created, so that a
+        compute-only pass before the first step has noise to run on"""
+        B = int(x.shape[0])
+        if self._drawn is None or int(self._drawn[1].shape[0]) != B:
+            self._drawn = self.model.draw_noise(B, self.noise_source, which="posterior", advance=False)
+        return self._drawn
+
+    def __call__(self, x, noise=None):
+        src = self.noise_source
+        if noise is None and src is None:
+            raise ValueError("TrainStep: pass the step's noise list, or build the step with noise_source=")
+        draw = noise is None
+        moved = self._must_move() or self._stale
+        self._stale = False
+        # (a step built with a source captures the draw into its graph: a call that brings its own list runs as eager launches)
+        if self.use_graph and self.graph_refused is None and (draw or src is None):
             if self._static is None:
-                self._static = (x.clone(), [e.clone() for e in noise])
+                self._static = (x.clone(), self._own_noise(x) if draw else [None if e is None else e.clone() for e in noise])
                 moved = True
             else:
                 sx, sn = self._static
-                if x.shape != sx.shape or x.dtype != sx.dtype or len(noise) != len(sn) or any(a.shape != b.shape for a, b in zip(noise, sn)):
+                if x.shape != sx.shape or x.dtype != sx.dtype:
+                    raise ValueError("TrainStep(graph=True): x and noise must keep the shapes of the first call")
+                if not draw and (len(noise) != len(sn) or any((a is None) != (b is None) or (a is not None and a.shape != b.shape) for a, b in zip(noise, sn))):
                     raise ValueError("TrainStep(graph=True): x and noise must keep the shapes of the first call")
                 sx.copy_(x)
-                for a, b in zip(sn, noise):
-                    a.copy_(b)
+                if not draw:
+                    for a, b in zip(sn, noise):
+                        if a is not None:           # (a slot the model does not read may be None, as CVAE1.forward allows)
+                            a.copy_(b)
             if moved:
                 self._capture()
             if self._graph is not None:
                 self._graph.replay()
                 return self._sobj
+        if draw:
+            noise = self._own_noise(x)
         if moved:
             self._move(x, noise)
-        return self._enqueue(x, noise)
+            self._stale = self._graph is not None        # objects switched kernels outside the graph: capture it again before its next replay
+        obj = self._enqueue(x, noise, draw=draw)
+        if src is not None and not draw:
+            src.skip(1)
+        return obj
 
     @property
     def skipped(self):

@@ -690,6 +690,56 @@ int iaf_axpby(const float* a, float sa, const float* b, float sb, float* out, si
 int iaf_affine_transform(const float* z, const float* m, const float* s, float scale, float* out, size_t n, void* stream);
 int iaf_clip(const float* x, float lo, float hi, float* out, size_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The device noise source.  The reference's DiagonalGaussian draws its own N(0,1) noise inside the graph
+ * (tf_utils/distributions.py:15-24); every eps / noise input above can be filled by this generator instead of by the caller.
+ * It is counter-based: a value depends on (seed, substream, step, element index) and on nothing else -- not on the launch shape,
+ * not on the other tensors of the call, not on the pointer's alignment.
+ *
+ * Definition.  Philox4x32-10 (multipliers D2511F53, CD9E8D57; key increments 9E3779B9, BB67AE85).  Element i of a tensor filled
+ * with (seed, substream, step, scale):
+ *     q = i / 4, m = i % 4;   key = (seed & 0xffffffff, seed >> 32);   ctr = (q, substream, step & 0xffffffff, step >> 32)
+ *     x0..x3 = philox(ctr, key);   for the pair a in {0, 1}:
+ *         u1 = ((x[2a] >> 8) + 1) 2^-24  in (0, 1],   u2 = (x[2a+1] >> 8) 2^-24  in [0, 1),   r = sqrt(-2 ln u1)
+ *         z[2a] = r cos(2 pi u2),   z[2a+1] = r sin(2 pi u2)
+ *     out[i] = scale * z[m]
+ * Both uniforms are exact in fp32; |z| <= sqrt(48 ln 2) = 5.768: the tails beyond that are cut off (probability 8e-9 per
+ * element).  The kernel uses the accurate log / sqrt / sincospi: results agree with an fp64 evaluation of the definition to 1e-5
+ * absolute (tests/test_hip_noise.py; tests/noise_reference.py is that evaluation in numpy).
+ * Known answers of Philox4x32-10 (counter / key -> output):
+ *     00000000 00000000 00000000 00000000 / 00000000 00000000 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     ffffffff ffffffff ffffffff ffffffff / ffffffff ffffffff -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * Known answers of the definition (scale 1), for a client to check itself:
+ *     seed 0, substream 0, step 0, elements 0..7:
+ *         0.9911375 -0.9246628 -0.6176091 -0.4820683 -0.1536381 0.1808259 0.8317351 0.1974396
+ *     seed 0x0123456789abcdef, substream 7, step 2^32 + 5, elements 1000..1005:
+ *         2.3193574 -0.1994520 1.3097198 -0.1905390 0.1468710 0.3309184
+ *
+ * iaf_rng_t holds the seed on the host and a 64-bit STEP COUNTER IN DEVICE MEMORY (0 after create).
+ * iaf_rng_fill_normal: ONE launch fills outs[0..n) (n <= 64; device fp32, counts[i] elements each, 1 <= counts[i] <= 2^34, any 4-byte
+ *   alignment) at the counter's current step; tensor i uses substreams[i] and scales[i] (scales = NULL: 1).  The table travels in
+ *   the kernel arguments: no upload, capturable.  The launch READS the step from device memory; advance != 0 enqueues a one-thread
+ *   launch behind it that adds 1.  A captured hipGraph holding such a call therefore draws fresh noise on every replay, with no
+ *   host code in between; advance = 0 draws at the current step and leaves the counter alone (the same numbers again next time).
+ * iaf_rng_seek / iaf_rng_skip: set the counter / add to it; enqueued on `stream` like every launch (capturable).
+ * iaf_rng_tell: the counter's value after everything enqueued on `stream` so far; SYNCHRONISES that stream; not during a capture
+ *   (hipErrorStreamCaptureUnsupported).
+ * One source is driven from one stream at a time (the counter is ordered by the stream).  Data-parallel ranks share the seed and
+ * take disjoint substreams (iaf_amd.NoiseSource: substream_base = rank << 16).
+ * Errors, before any device work: IAF_ERR_NULL (handle, table or entry), IAF_ERR_SHAPE (n < 1, n > 64, a count of 0 or above 2^34),
+ * IAF_ERR_WORKSPACE (an output not 4-byte aligned).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct iaf_rng iaf_rng_t;
+#define IAF_RNG_MAX_TENSORS 64
+int iaf_rng_create(iaf_rng_t** out, uint64_t seed);
+int iaf_rng_destroy(iaf_rng_t* r);
+int iaf_rng_fill_normal(iaf_rng_t* r, float* const* outs, const size_t* counts, const unsigned* substreams, const float* scales,
+                        int n, int advance, void* stream);
+int iaf_rng_seek(iaf_rng_t* r, uint64_t step, void* stream);
+int iaf_rng_skip(iaf_rng_t* r, uint64_t steps, void* stream);
+int iaf_rng_tell(iaf_rng_t* r, uint64_t* step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
