@@ -77,6 +77,10 @@ SIGNATURES = {
     "iaf_skip_counter_destroy": (ctypes.c_int, [_vp]),
     "iaf_nonfinite_scan": (ctypes.c_int, [_c_float_p, ctypes.c_size_t, _c_float_p, ctypes.c_int, _vp, _vp]),
     "iaf_adamax_ema_step_guarded": (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_size_t] + [ctypes.c_float] * 6 + [_vp, _vp, _vp]),
+    "iaf_nonfinite_scan_sumsq": (ctypes.c_int, [_c_float_p, ctypes.c_size_t, _c_float_p, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "iaf_train_summaries_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "iaf_train_summaries_reset": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "iaf_train_summaries": (ctypes.c_int, [_c_float_p] * 5 + [_vp, ctypes.c_float, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "iaf_posterior_block_forward": (ctypes.c_int, [_vp] + [_c_float_p] * 9 + [ctypes.c_float] + [_c_float_p] * 4 +
                                     [ctypes.c_int] * 3 + [_vp, ctypes.c_size_t, _vp]),
     "iaf_gaussian_sample": (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_size_t, _vp]),

@@ -2751,6 +2751,44 @@ extern "C" int iaf_nonfinite_scan(const float* buf, size_t n, const float* extra
     return (int)hipGetLastError();
 }
 
+extern "C" int iaf_nonfinite_scan_sumsq(const float* buf, size_t n, const float* extra, int n_extra, unsigned* guard, double* partials,
+                                        double* sumsq, void* stream) {
+    if (!guard || !partials || !sumsq || (n && !buf) || n_extra < 0 || (n_extra && !extra)) return IAF_ERR_NULL;
+    if (n_extra > 256) return IAF_ERR_SHAPE;                 // (the extras are read by the first workgroup's lanes)
+    if ((((uintptr_t)guard | (uintptr_t)partials | (uintptr_t)sumsq) & 7) != 0) return IAF_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n4 = ((uintptr_t)buf & 15) == 0 ? n / 4 : 0;
+    // (the scan's grid: at most 2048 workgroups, one slot of `partials` each)
+    hipLaunchKernelGGL(iaf_guard_sumsq_scan_kernel, ew_grid((n4 ? n4 : n) > (size_t)n_extra ? (n4 ? n4 : n) : (size_t)n_extra), dim3(256), 0,
+                       st, buf, n4, n, extra, n_extra, guard, partials, sumsq);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t iaf_train_summaries_bytes(int n_layers) {
+    if (n_layers < 1 || n_layers > IAF_SUMMARY_MAX_LAYERS) return 0;
+    return (size_t)(2 * (6 + 2 * n_layers) + 2) * 8;
+}
+
+extern "C" int iaf_train_summaries_reset(void* record, int n_layers, void* stream) {
+    if (!record) return IAF_ERR_NULL;
+    if (n_layers < 1 || n_layers > IAF_SUMMARY_MAX_LAYERS) return IAF_ERR_SHAPE;
+    if (((uintptr_t)record & 7) != 0) return IAF_ERR_WORKSPACE;
+    hipLaunchKernelGGL(iaf_train_summaries_reset_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)record,
+                       (int)(iaf_train_summaries_bytes(n_layers) / 8));
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_train_summaries(const float* layer_obj, const float* layer_cost, const float* log_pxz, const float* dec_log_stdv,
+                                   const float* loss_all, const double* sumsq, float grad_scale, const unsigned* guard, void* record,
+                                   int n_layers, int n, void* stream) {
+    if (!layer_obj || !layer_cost || !log_pxz || !dec_log_stdv || !loss_all || !sumsq || !guard || !record) return IAF_ERR_NULL;
+    if (n_layers < 1 || n_layers > IAF_SUMMARY_MAX_LAYERS || n < 1) return IAF_ERR_SHAPE;
+    if ((((uintptr_t)record | (uintptr_t)sumsq) & 7) != 0) return IAF_ERR_WORKSPACE;
+    hipLaunchKernelGGL(iaf_train_summaries_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, layer_obj, layer_cost, log_pxz, dec_log_stdv,
+                       loss_all, sumsq, grad_scale, guard, (double*)record, n_layers, n);
+    return (int)hipGetLastError();
+}
+
 extern "C" int iaf_adamax_ema_step_guarded(float* var, const float* grad, float* slot_m, float* slot_v, float* ema, size_t n,
                                            float lr, float beta1, float beta2, float eps, float ema_decay, float grad_scale,
                                            const unsigned* guard, iaf_skip_counter_t* skips, void* stream) {

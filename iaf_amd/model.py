@@ -521,9 +521,13 @@ class CVAE1(object):
         self._segs = segs
         return names
 
-    def fb_begin(self, x, noise, grads=None, autotune=False):
+    def fb_begin(self, x, noise, grads=None, autotune=False, terms=False):
         """forward_backward, first part: the forward pass (keeping what the backward reads) and the backward of the top end --
-        obj = sum(kl_obj - log_pxz), likelihood, clip, x_dec (tf_train.py:206-211).  Then fb_segment(0 .. n_buckets-1)."""
+        obj = sum(kl_obj - log_pxz), likelihood, clip, x_dec (tf_train.py:206-211).  Then fb_segment(0 .. n_buckets-1).
+        terms=True also keeps what the reference's summaries are made of (tf_train.py:203-204, 214-218), under "terms" in the returned
+        dict: layer_obj / layer_cost [nl, n] (every layer's kl_obj / kl_cost, top-down as the down pass runs), layers (the (i, j) of
+        each table row), log_pxz [n] and loss [1] = sum(kl_cost - log_pxz) (what compute_lowerbound sums to at k = 1; two launches more: one iaf_colsum, one iaf_sum_axpy).  terms=False: not one launch
+        more."""
         if not getattr(self, "_training", False) or self.params is None:
             raise RuntimeError("CVAE1.set_training(True), then load(params), before forward_backward")
         if self.k != 1 or self.mode != "train":
@@ -545,11 +549,12 @@ class CVAE1(object):
         St = S // 2 ** self.depth
         h = torch.empty((n, hs, St, St), **f32)
         _capi.check(lib.iaf_tile_channels(_ptr(p["h_top"]), _ptr(h), n, hs, St * St, st()))
-        objs, li = [], 0
+        objs, costs, li = [], [], 0
         for level in reversed(self.layers):
             for layer in reversed(level):
-                h, cur_obj, _ = layer.down_train(h, noise[2 * li + 1], autotune=autotune)
+                h, cur_obj, cur_cost = layer.down_train(h, noise[2 * li + 1], autotune=autotune)
                 objs.append(cur_obj)
+                costs.append(cur_cost)
                 li += 1
         h_last = h
         objs = torch.stack(objs)
@@ -562,6 +567,15 @@ class CVAE1(object):
         log_pxz = discretized_logistic(x_out, p["dec_log_stdv"], sample=xf)
         obj = torch.empty(1, **f32)
         _capi.check(lib.iaf_sum_axpy(_ptr(kl_obj), _ptr(log_pxz), -1.0, _ptr(obj), n, st()))
+        kept = None
+        if terms:                                                    # loss = sum(kl_cost - log_pxz), as obj above (tf_train.py:218, k = 1)
+            costs = torch.stack(costs)
+            kl_cost = torch.empty(n, **f32)
+            _capi.check(lib.iaf_colsum(_ptr(costs), _ptr(kl_cost), li, n, st()))
+            loss = torch.empty(1, **f32)
+            _capi.check(lib.iaf_sum_axpy(_ptr(kl_cost), _ptr(log_pxz), -1.0, _ptr(loss), n, st()))
+            kept = dict(layer_obj=objs, layer_cost=costs, log_pxz=log_pxz, loss=loss, kl_cost=kl_cost,
+                        layers=[(i, j) for i in reversed(range(self.depth)) for j in reversed(range(self.num_blocks))])
         # ---- backward of the top end: obj = sum(kl_obj - log_pxz)  (tf_train.py:206-211)
         grads = {} if grads is None else grads
         gs = lambda nm: grads.setdefault(nm, torch.empty_like(p[nm]))
@@ -591,6 +605,8 @@ class CVAE1(object):
                 lgrads[(i, j)] = {k[len(pre):]: v for k, v in grads.items() if k.startswith(pre)}
         self._fb = dict(x_out=x_out, obj=obj, grads=grads, lgrads=lgrads, d=d, xf=xf, n=n, S=S, St=St, autotune=autotune,
                         dko=torch.ones(n, **f32), keep=(dW, scratch, zero_b, t, d_xout, dls_rows, logscale, log_pxz, kl_obj, objs))
+        if kept is not None:
+            self._fb["terms"] = kept
         return self._fb
 
     def fb_segment(self, si):

@@ -19,6 +19,7 @@ the skip counter rise, every object whose range word is newly set is moved throu
 passes on the call's inputs, no collective, no update) and the graph is captured again on the same stream; from then on the
 step runs where it did not overflow."""
 import ctypes
+import inspect
 import math
 import warnings
 
@@ -87,10 +88,21 @@ class TrainStep(object):
     every replay draws fresh noise and no launch or copy precedes the graph).  Call t (t = 0, 1, ...) uses step s0 + t of the source,
     s0 being where the source stood at the first call, whatever was skipped or captured again: the compute-only passes (warm-up,
     recovery) run on what the buffers hold and never advance the source.  ts(x, noise) with a list still works: that call runs as eager
-    launches on the list and moves the source on by one like any other call."""
+    launches on the list and moves the source on by one like any other call.
+
+    summaries=True: the step also produces the numbers the reference loop fetches and logs (tf_train.py:142, 148-149, 203-204,
+    214-216, 268-285) -- with launches of the step itself (in graph mode inside the captured graph) that accumulate in device memory,
+    so no step waits for the host.  The model's fb_begin must take terms=True and return "terms" (CVAE1 does), and the model needs
+    image_size.  The local loss travels in the status word's second slot through the all-reduce the objective already makes.
+    ts.summaries(reset=True) synchronises and returns the means over the accepted steps since the last reset (NaN when there were
+    none) under the reference's tags -- model/bits_per_dim, model/dec_log_stdv, model/log_pxz, model/kl_obj, model/kl_cost,
+    model/kl_obj_%02d_%02d, model/kl_cost_%02d_%02d -- plus grad_norm (the norm of the averaged gradient), steps and skipped;
+    ts.last_summaries() the same keys for the most recent step alone, accepted or not."""
+
+    _FIXED = ("model/bits_per_dim", "model/dec_log_stdv", "model/log_pxz", "model/kl_obj", "model/kl_cost", "grad_norm")
 
     def __init__(self, model, lr, n_buckets=1, comm=None, graph=True, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.999,
-                 noise_source=None):
+                 noise_source=None, summaries=False):
         if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0:
             raise ValueError("lr must be a positive finite number, got %r" % (lr,))
         if isinstance(n_buckets, bool) or not isinstance(n_buckets, int) or n_buckets < 1:
@@ -102,8 +114,21 @@ class TrainStep(object):
                 raise ValueError("%s must lie in [0, 1), got %r" % (nm, v))
         if not (isinstance(eps, (int, float)) and math.isfinite(eps) and eps >= 0):
             raise ValueError("eps must be a finite number >= 0, got %r" % (eps,))
+        if not isinstance(summaries, bool):
+            raise ValueError("summaries must be True or False, got %r" % (summaries,))
         if getattr(model, "params", None) is None:
             raise RuntimeError("TrainStep: model.set_training(True), then model.load(params), first")
+        if summaries:
+            try:
+                takes = "terms" in inspect.signature(model.fb_begin).parameters
+            except (TypeError, ValueError):
+                takes = False
+            if not takes:
+                raise ValueError("TrainStep(summaries=True): the model's fb_begin takes no terms= (it cannot say what the summaries are made of)")
+            if not isinstance(getattr(model, "image_size", None), int) or model.image_size < 1:
+                raise ValueError("TrainStep(summaries=True): the model needs image_size (bits per dim are per pixel)")
+            if "dec_log_stdv" not in model.params:
+                raise ValueError("TrainStep(summaries=True): the model has no dec_log_stdv variable")
         self.model, self.lr = model, float(lr)
         self._hyper = (float(beta1), float(beta2), float(eps), float(ema_decay))
         self.flat = FlatParams({k: model.params[k] for k in model.completion_order()})
@@ -140,14 +165,29 @@ class TrainStep(object):
         self._static = None
         self._stale = False               # the captured graph must be captured again before its next replay
         self._stream = torch.cuda.Stream(device=dev) if graph else None
+        self.with_summaries = summaries
+        self._terms = None                # the step's terms (fb_begin(terms=True)["terms"]); the captured graph reads these very tensors
+        self._rec = None                  # the record: device memory (iaf_train_summaries), or a dict of host fp64 arrays
 
     # -- the step's launches ------------------------------------------------------------------------------------------------------
     def _compute(self, x, noise):
         """forward and backward only: no collective, no update (the passes that move objects whose range word is set)"""
         self.model.prepare_weights()
-        self.model.fb_begin(x, noise, grads=self.flat.g)
+        self._begin(x, noise)
         for i in range(self.n_buckets):
             self.model.fb_segment(i)
+
+    def _begin(self, x, noise):
+        """fb_begin; with summaries also the step's terms, the local loss into the status word's second slot and, the first time, the
+        record (a compute-only pass precedes every capture, so the record is never allocated or zeroed inside one)"""
+        if not self.with_summaries:
+            return self.model.fb_begin(x, noise, grads=self.flat.g)
+        fb = self.model.fb_begin(x, noise, grads=self.flat.g, terms=True)
+        if "terms" not in fb:
+            raise ValueError("TrainStep(summaries=True): the model's fb_begin returned no \"terms\"")
+        self._set_terms(fb["terms"])
+        self._status[1:2].copy_(self._terms["loss"].reshape(1))
+        return fb
 
     def _enqueue(self, x, noise, draw=False):
         """one whole step on the current stream; returns the objective.  draw: `noise` is the step's own buffer set, and the step's
@@ -158,7 +198,7 @@ class TrainStep(object):
             m.draw_noise(int(x.shape[0]), self.noise_source, which="posterior", out=noise)
         try:
             m.prepare_weights()
-            obj = m.fb_begin(x, noise, grads=flat.g)["obj"]
+            obj = self._begin(x, noise)["obj"]
             self._status[:1].copy_(obj.reshape(1))
             red.reduce_tensor(self._status)
             status_sent = True
@@ -184,20 +224,75 @@ class TrainStep(object):
         self._update()
         return obj
 
+    def _set_terms(self, terms):
+        """keep the step's terms and, at the first step, make the record for their geometry (nl layers, n batch rows)"""
+        lo, lc, lp = terms["layer_obj"], terms["layer_cost"], terms["log_pxz"]
+        nl, n = int(lo.shape[0]), int(lo.shape[1])
+        if tuple(lc.shape) != (nl, n) or lp.numel() != n or len(terms["layers"]) != nl or terms["loss"].numel() != 1:
+            raise ValueError("TrainStep: terms must hold layer_obj / layer_cost [nl, n], log_pxz [n], loss [1] and nl (i, j) pairs")
+        self._terms = terms
+        if self._rec is not None:
+            if (nl, n) != self._geom:
+                raise ValueError("TrainStep(summaries=True): the batch size and the layers must stay those of the first step")
+            return
+        self._geom = (nl, n)
+        self._tags = list(self._FIXED)
+        for (i, j) in terms["layers"]:
+            self._tags += ["model/kl_obj_%02d_%02d" % (i, j), "model/kl_cost_%02d_%02d" % (i, j)]
+        F = 6 + 2 * nl
+        if self.on_device:
+            lib, dev = _capi.lib(), self.flat.params.device
+            nbytes = int(lib.iaf_train_summaries_bytes(nl))
+            if nbytes != (2 * F + 2) * 8:
+                raise ValueError("TrainStep(summaries=True): %d layers are more than the record holds" % nl)
+            # (allocated outside any capture's pool by the warm-up pass that precedes every capture; zeroed by torch, no launch of ours)
+            self._rec = torch.zeros(2 * F + 2, dtype=torch.float64, device=dev)
+            self._partials = torch.zeros(2048, dtype=torch.float64, device=dev)
+            self._sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
+        else:
+            self._rec = dict(acc=torch.zeros(F, dtype=torch.float64), last=torch.zeros(F, dtype=torch.float64), steps=0, skipped=0)
+
+    def _host_fields(self):
+        """the record's fields of this step with torch fp64 ops (host replicas)"""
+        t, f64 = self._terms, torch.float64
+        lo, lc = t["layer_obj"].to(f64).mean(dim=1), t["layer_cost"].to(f64).mean(dim=1)
+        norm = (1.0 / self.world) * torch.sqrt((self.flat.grads.to(f64) ** 2).sum())
+        head = [self._status[1].to(f64), self.model.params["dec_log_stdv"].reshape(-1)[0].to(f64), -t["log_pxz"].to(f64).mean(), lo.sum(),
+                lc.sum(), norm]
+        return torch.cat([torch.stack(head), torch.stack([lo, lc], dim=1).reshape(-1)])
+
     def _update(self):
         flat, (b1, b2, eps, decay) = self.flat, self._hyper
+        summ = self.with_summaries and self._terms is not None      # (no terms: the very first step could not finish its compute)
         if self.on_device:
             lib = _capi.lib()
             ptr = lambda t: ctypes.c_void_p(t.data_ptr())
             st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _capi.check(lib.iaf_nonfinite_scan(ptr(flat.grads), flat.grads.numel(), ptr(self._status), 1, ptr(self._guard), st))
+            if summ:
+                t, (nl, n) = self._terms, self._geom
+                _capi.check(lib.iaf_nonfinite_scan_sumsq(ptr(flat.grads), flat.grads.numel(), ptr(self._status), 1, ptr(self._guard),
+                                                         ptr(self._partials), ptr(self._sumsq), st))
+                _capi.check(lib.iaf_train_summaries(ptr(t["layer_obj"]), ptr(t["layer_cost"]), ptr(t["log_pxz"]),
+                                                    ptr(self.model.params["dec_log_stdv"]), ctypes.c_void_p(self._status.data_ptr() + 4),
+                                                    ptr(self._sumsq), 1.0 / self.world, ptr(self._guard), ptr(self._rec), nl, n, st))
+            else:
+                _capi.check(lib.iaf_nonfinite_scan(ptr(flat.grads), flat.grads.numel(), ptr(self._status), 1, ptr(self._guard), st))
             _capi.check(lib.iaf_adamax_ema_step_guarded(ptr(flat.params), ptr(flat.grads), ptr(flat.slot_m), ptr(flat.slot_v),
                                                         ptr(flat.ema), flat.params.numel(), self.lr, b1, b2, eps, decay,
                                                         1.0 / self.world, ptr(self._guard), self._skips._h, st))
             # (raw-pointer writes: tell torch, as FlatParams.adamax_ema_step does)
             torch.autograd.graph.increment_version((flat.params, flat.ema, flat.slot_m, flat.slot_v))
         else:        # host replicas: the same decision with torch ops
-            if bool(torch.isfinite(flat.grads).all()) and bool(torch.isfinite(self._status[:1]).all()):
+            ok = bool(torch.isfinite(flat.grads).all()) and bool(torch.isfinite(self._status[:1]).all())
+            if summ:
+                rec = self._rec
+                rec["last"] = self._host_fields()
+                if ok:
+                    rec["acc"] = rec["acc"] + rec["last"]
+                    rec["steps"] += 1
+                else:
+                    rec["skipped"] += 1
+            if ok:
                 flat.adamax_ema_step(self.lr, world=self.world, beta1=b1, beta2=b2, eps=eps, ema_decay=decay)
             else:
                 self._host_skips += 1
@@ -318,6 +413,58 @@ class TrainStep(object):
         if self.on_device:
             torch.cuda.synchronize()
         return self._count()
+
+    # -- summaries ------------------------------------------------------------------------------------------------------------------
+    def _read_record(self):
+        """(acc, last, steps, skipped) on the host, after everything enqueued so far has run"""
+        if not self.with_summaries:
+            raise RuntimeError("TrainStep: built without summaries=True")
+        if self._rec is None:
+            return None
+        if not self.on_device:
+            r = self._rec
+            return r["acc"].numpy().copy(), r["last"].numpy().copy(), r["steps"], r["skipped"]
+        torch.cuda.current_stream().synchronize()
+        if self._stream is not None:
+            self._stream.synchronize()
+        F = 6 + 2 * self._geom[0]
+        host = self._rec.cpu()
+        counts = host[2 * F:].view(torch.int64)
+        return host[:F].numpy().copy(), host[F:2 * F].numpy().copy(), int(counts[0]), int(counts[1])
+
+    def _as_dict(self, fields, steps, skipped):
+        S, n = self.model.image_size, self._geom[1]
+        vals = [float(v) for v in fields]
+        vals[0] = vals[0] / (math.log(2.) * 3 * S * S * n * self.world)            # tf_train.py:142
+        out = dict(zip(self._tags, vals))
+        out["steps"], out["skipped"] = steps, skipped
+        return out
+
+    def summaries(self, reset=True):
+        """the means over the accepted steps since the last reset (NaN with steps == 0), steps and skipped; synchronises.  reset=True
+        then zeroes the record with a stream-ordered launch (outside any capture): the whole record, `last` included, so read
+        last_summaries() before a resetting call if the most recent step's numbers are wanted."""
+        rec = self._read_record()
+        if rec is None:
+            raise RuntimeError("TrainStep.summaries: no step has run yet")
+        acc, _, steps, skipped = rec
+        mean = acc / steps if steps else acc * float("nan")
+        if reset:
+            if self.on_device:
+                st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                _capi.check(_capi.lib().iaf_train_summaries_reset(ctypes.c_void_p(self._rec.data_ptr()), self._geom[0], st))
+            else:
+                self._rec.update(acc=torch.zeros_like(self._rec["acc"]), last=torch.zeros_like(self._rec["last"]), steps=0, skipped=0)
+        return self._as_dict(mean, steps, skipped)
+
+    def last_summaries(self):
+        """the same keys for the most recent step alone, accepted or skipped (steps / skipped: the record's counts); synchronises.  After
+        summaries(reset=True) and before the next step every value is 0: the reset zeroes the whole record."""
+        rec = self._read_record()
+        if rec is None:
+            raise RuntimeError("TrainStep.last_summaries: no step has run yet")
+        _, last, steps, skipped = rec
+        return self._as_dict(last, steps, skipped)
 
     @property
     def graphed(self):

@@ -233,6 +233,33 @@ int iaf_adamax_ema_step_guarded(float* var, const float* grad, float* slot_m, fl
                                 float beta1, float beta2, float eps, float ema_decay, float grad_scale, const unsigned* guard,
                                 iaf_skip_counter_t* skips, void* stream);
 
+/* Training summaries without a host round trip (tf_train.py:142, 148-149, 203-204, 214-216, 268-285): the numbers of a step are
+ * produced by launches that sit in the step's captured hipGraph and accumulate in device memory; the host reads the record when it
+ * wants to (e.g. every 20 steps).
+ *   iaf_nonfinite_scan_sumsq is iaf_nonfinite_scan (same verdict in guard[0], same arrival word, back to 0 afterwards) that also
+ *   writes sumsq[0] = sum_i buf[i]^2 from the same single read of buf.  Squares and sums are fp64 (the square of an fp32 value is
+ *   exact; entries of 1e25 do not overflow), with no float atomics: every workgroup stores one partial into its own slot of
+ *   `partials` (>= 2048 doubles of device memory, 8-byte aligned, no initial value needed) and the last workgroup to arrive adds
+ *   the slots in a fixed order, so sumsq is bit-identical from call to call and replay to replay for a given n and alignment of
+ *   buf.  A non-finite entry makes sumsq non-finite.  One scan at a time per (guard, partials).  guard is the scan's above (4 words,
+ *   8-byte aligned, zero when first used) and sumsq 8-byte aligned; anything else is IAF_ERR_WORKSPACE.
+ *   The record of a model with n_layers stochastic layers is iaf_train_summaries_bytes(n_layers) bytes (0: n_layers outside
+ *   1..256), 8-byte aligned: double acc[F], double last[F], uint64 steps, uint64 skipped, F = 6 + 2 n_layers, fields
+ *     [0] loss_all[0], the all-reduced loss (sum over ranks of sum_b (kl_cost - log_pxz))    [1] dec_log_stdv[0]
+ *     [2] -mean_b log_pxz    [3] mean_b kl_obj = sum_l mean_b layer_obj[l]    [4] mean_b kl_cost    [5] grad_scale * sqrt(sumsq[0])
+ *     [6 + 2l] mean_b layer_obj[l]    [7 + 2l] mean_b layer_cost[l]
+ *   from layer_obj / layer_cost [n_layers][n] (the layers' kl_obj / kl_cost, any fixed order), log_pxz [n]; means in fp64.
+ *   iaf_train_summaries always writes `last`; with guard[0] == 0 it adds the fields to acc and 1 to steps, with guard[0] != 0 it
+ *   leaves acc untouched and adds 1 to skipped.  iaf_train_summaries_reset zeroes the whole record (stream-ordered; a new record
+ *   must be reset once).  One workgroup each; the record is plain device memory, read it with a copy after synchronising. */
+int iaf_nonfinite_scan_sumsq(const float* buf, size_t n, const float* extra, int n_extra, unsigned* guard, double* partials,
+                             double* sumsq, void* stream);
+size_t iaf_train_summaries_bytes(int n_layers);
+int iaf_train_summaries_reset(void* record, int n_layers, void* stream);
+int iaf_train_summaries(const float* layer_obj, const float* layer_cost, const float* log_pxz, const float* dec_log_stdv,
+                        const float* loss_all, const double* sumsq, float grad_scale, const unsigned* guard, void* record,
+                        int n_layers, int n, void* stream);
+
 /* Full posterior block, tf_train.py:56-85 (mode "train"): everything between down_conv1 and
  * the concat, i.e. posterior sample, logqs, IAF step, log-det accumulation, prior logps, KL and
  * free bits.  All [B,n_z,H,W] inputs NCHW; up_context/down_context [B,n_h,H,W]; eps is the

@@ -9,10 +9,16 @@ back-to-back replays between HIP events on the current stream):
 then forces one re-capture of the guarded step (the path a skip takes after an object moved to bf16 planes) and times it again: a
 re-captured step that is slower than the first capture by more than 2 % is reported as probably running the recomputing one-launch
 step instead of the halo exchange (the exchange sets of a stream stay marked as captured: include/iaf_hip.h).
+--summaries adds, before the re-capture: a second model and TrainStep(summaries=True) on a stream of its own, its replay timed in
+alternation with the guarded replay (summaries_ms against guarded_alt_ms), and iaf_nonfinite_scan_sumsq in alternation with
+iaf_nonfinite_scan on the same gradient buffer (fused_scan_us against scan_alt_us), then reads the record once.  The second model
+and its flat state (parameters, gradients, slots, EMA) live next to the first in the same process: about 1.3 GB more device memory at
+the default geometry.  It replays the TrainStep's private graph (ts._graph) to time the step without the input copies.
 Prints one JSON line."""
 import argparse
 import ctypes
 import json
+import math
 import os
 import sys
 import time
@@ -41,6 +47,7 @@ def main():
     ap.add_argument("--num-blocks", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--summaries", action="store_true", help="also time the step and the scan with training summaries")
     args = ap.parse_args()
     import torch
     import golden_inputs as gi
@@ -109,6 +116,51 @@ def main():
     scan = lambda: _capi.check(lib.iaf_nonfinite_scan(P(flat.grads), flat.grads.numel(), P(ts._status), 1, P(guard), st()))
     scan()
     scan_us = 1e3 * float(np.median([timed(scan, 50) for _ in range(5)]))
+    extra = {}
+    if args.summaries:
+        model2 = iaf_amd.CVAE1(z_size=zs, h_size=hs, kl_min=0.25, depth=2, num_blocks=nb, k=1, image_size=32)
+        model2.set_training(True)
+        model2.load({k: dev(v) for k, v in c["params"].items()})
+        ts2 = iaf_amd.TrainStep(model2, lr, graph=True, summaries=True)
+        for tune in (True, False):
+            model2.prepare_weights()
+            model2.fb_begin(x, noise, grads=ts2.flat.g, autotune=tune)
+            for i in range(ts2.n_buckets):
+                model2.fb_segment(i)
+        torch.cuda.synchronize()
+        ts2(x, noise)
+        torch.cuda.synchronize()
+        if not ts2.graphed:
+            raise SystemExit("train_step_bench: the step with summaries was not captured (%s)" % ts2.graph_refused)
+        with_s = lambda: ts2._graph.replay()
+        for _ in range(3):
+            guarded()
+            with_s()
+        ta, tb = [], []
+        for _ in range(args.rounds):
+            ta.append(timed(guarded, args.reps))
+            tb.append(timed(with_s, args.reps))
+        ma, mb = float(np.median(ta)), float(np.median(tb))
+        partials = torch.zeros(2048, dtype=torch.float64, device="cuda")
+        sumsq = torch.zeros(1, dtype=torch.float64, device="cuda")
+        fused = lambda: _capi.check(lib.iaf_nonfinite_scan_sumsq(P(flat.grads), flat.grads.numel(), P(ts._status), 1, P(guard), P(partials),
+                                                                 P(sumsq), st()))
+        fused()
+        sa, sb = [], []
+        for _ in range(5):
+            sa.append(1e3 * timed(scan, 50))
+            sb.append(1e3 * timed(fused, 50))
+        msa, msb = float(np.median(sa)), float(np.median(sb))
+        norm = float(torch.sqrt((flat.grads.double() ** 2).sum()).item())
+        rec = ts2.summaries(reset=False)
+        extra = {"summaries_ms": mb, "guarded_alt_ms": ma, "summaries_overhead_ms": mb - ma, "summaries_overhead_frac": (mb - ma) / ma,
+                 "summaries_repeats_ms": tb, "guarded_alt_repeats_ms": ta, "fused_scan_us": msb, "scan_alt_us": msa,
+                 "fused_over_plain_scan": msb / msa, "fused_scan_repeats_us": sb, "scan_alt_repeats_us": sa,
+                 "fused_scan_gbs": 4 * flat.grads.numel() / (msb * 1e-6) / 1e9,
+                 "fused_scan_norm_rel_err": abs(math.sqrt(float(sumsq.item())) - norm) / norm,
+                 "summaries_captures": ts2.captures, "summaries_record": {k: rec[k] for k in ("model/bits_per_dim", "model/dec_log_stdv", "model/log_pxz",
+                                                                                                "model/kl_obj", "model/kl_cost", "grad_norm", "steps", "skipped")}}
+        del ts2, model2
     # one re-capture of the guarded step, as after a skip that moved an object to bf16 planes
     t0 = time.perf_counter()
     ts._capture()
@@ -122,7 +174,7 @@ def main():
     skipped = ts.skipped
     obj = float(ts._sobj.item())
     print(json.dumps({
-        "tool": "train_step_bench", "B": B, "z": zs, "h": hs, "depths": [nb, nb], "params": int(flat.params.numel()),
+        **extra, "tool": "train_step_bench", "B": B, "z": zs, "h": hs, "depths": [nb, nb], "params": int(flat.params.numel()),
         "flat_mb": 4e-6 * flat.params.numel(),
         "guarded_ms": mg, "unguarded_ms": mp, "guard_overhead_ms": mg - mp, "guard_overhead_frac": (mg - mp) / mp,
         "scan_us": scan_us, "scan_gbs": 4 * flat.grads.numel() / (scan_us * 1e-6) / 1e9,
