@@ -285,6 +285,11 @@ extern "C" int iaf_sum_axpy(const float* a, const float* b, float sb, float* out
 // tf_train.py:211), with clip_by_value's gradient folded in (:208: the gradient passes where the value was not clipped).
 //   s = (floor(x / b) b - mean) / scale,  t = s + b / scale,  P = sig(t) - sig(s) + 1e-7,  logp = log P
 //   d logp / d mean = -(sig'(t) - sig'(s)) / (scale P);   d logp / d logscale = (-t sig'(t) + s sig'(s)) / P
+// Evaluated as iaf_disc_logistic_kernel evaluates the forward, so that this is the gradient of the number the engine computes:
+// e = exp(-|u|) gives sig(|u|) = 1 / (1 + e) and sig(-|u|) = e / (1 + e) each directly, sig'(u) = sig(u) sig(-u), and where s > 0
+// P - 1e-7 = sig(-s) - sig(-t), the side on which both terms are small.  (The literal fp32 form -- sig(t) - sig(s) and
+// sig (1 - sig) with both sigmoids next to 1 -- cancels to ~1e-7 absolute in the upper tail, the size of the floor: d_mean was off
+// by tens of per cent of its largest entry at dec_log_stdv <= -4.)
 // One workgroup per row; d_logscale_rows[b] = up * sum over the row (summed over rows by iaf_sum_axpy).
 __global__ __launch_bounds__(256) void iaf_discretized_logistic_bwd_kernel(const float* __restrict__ mean, const float* __restrict__ logscale,
                                                                           const float* __restrict__ sample, float up, float clip_lo,
@@ -292,15 +297,17 @@ __global__ __launch_bounds__(256) void iaf_discretized_logistic_bwd_kernel(const
                                                                           float* __restrict__ d_logscale_rows, size_t n_per_row,
                                                                           float binsize) {
     __shared__ float red[256];
-    const float scale = __expf(logscale[0]), inv = 1.0f / scale;
+    const float scale = expf(logscale[0]), inv = 1.0f / scale;
     const size_t base = (size_t)blockIdx.x * n_per_row;
     float acc = 0.f;
     for (size_t i = threadIdx.x; i < n_per_row; i += 256) {
         const float m = mean[base + i];
         const float s = (floorf(sample[base + i] / binsize) * binsize - m) * inv, t = s + binsize * inv;
-        const float ss = 1.0f / (1.0f + __expf(-s)), st = 1.0f / (1.0f + __expf(-t));
-        const float P = st - ss + 1e-7f;
-        const float ds = ss * (1.0f - ss), dt = st * (1.0f - st);
+        const float es = expf(-fabsf(s)), et = expf(-fabsf(t));
+        const float rs = 1.0f / (1.0f + es), rt = 1.0f / (1.0f + et);      // sig(|s|), sig(|t|)
+        const float ls = es * rs, lt = et * rt;                            // sig(-|s|), sig(-|t|)
+        const float P = (s > 0.f ? ls - lt : (t >= 0.f ? rt : lt) - ls) + 1e-7f;
+        const float ds = ls * rs, dt = lt * rt;
         const bool pass = !(clip_lo < clip_hi) || (m > clip_lo && m < clip_hi);
         d_mean[base + i] = pass ? up * (-(dt - ds) * inv / P) : 0.f;
         acc += (-t * dt + s * ds) / P;
