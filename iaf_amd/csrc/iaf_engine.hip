@@ -128,6 +128,7 @@ struct iaf_stack {
     unsigned* xch_err_dev = nullptr;      // ... without synchronising; its device-side alias
     bool xch_on = true;                   // iaf_stack_set_halo_exchange
     unsigned xch_knob = 0;                // iaf_stack_set_halo_exchange_debug
+    int fb_groups = 1;                    // iaf_stack_set_free_bits_groups: the posterior block's free-bits mean per contiguous run of B / fb_groups rows
     int precision = IAF_PRECISION_BF16X3;   // forward convs: bf16x3 split products on the bf16 MFMA, or the exact fp32 MFMA
     int fuse_first = 2;       // first masked conv fused into the second one's kernel: 0 never, 1 whenever possible, 2 only where
                               // iaf_stack_autotune measured it faster (on MI355X at the BASELINE sizes it is not: docs/LAB_NOTEBOOK_r01-r03.md 4.8)
@@ -558,6 +559,19 @@ extern "C" int iaf_stack_set_halo_exchange(iaf_stack_t* s, int on) {
     if (!s) return IAF_ERR_NULL;
     s->xch_on = on != 0;
     return xch_reset_sets(s);                                // a fresh start either way: error words cleared
+}
+
+extern "C" int iaf_stack_set_free_bits_groups(iaf_stack_t* s, int groups) {
+    if (!s) return IAF_ERR_NULL;
+    if (groups < 1 || groups > IAF_MAX_FREE_BITS_GROUPS) return IAF_ERR_SHAPE;
+    if (groups > 1 && s->variant != IAF_VARIANT_TF) return IAF_ERR_UNSUPPORTED;      // (the Theano objective is one scalar per layer, models.py:458-461)
+    s->fb_groups = groups;
+    return IAF_OK;
+}
+extern "C" int iaf_stack_get_free_bits_groups(const iaf_stack_t* s, int* groups) {
+    if (!s || !groups) return IAF_ERR_NULL;
+    *groups = s->fb_groups;
+    return IAF_OK;
 }
 
 extern "C" int iaf_stack_set_halo_exchange_debug(iaf_stack_t* s, unsigned knobs) {
@@ -1348,7 +1362,7 @@ static int step_threads(step_fn_t fn) {
 // kl_part: posterior mode only -- per-(row block, channel) sums of the KL elements, [B * nrb][n_z] (StepP::kl_part)
 // fin (posterior mode, optional): where the block's free-bits results go if the launch can finish them itself (StepP::fin_*); *fin->done
 // tells the caller whether it did -- else the caller runs launch_kl_from_parts behind the launch as before
-struct StepFin { float* kl_obj; float* kl_cost; float kl_min; bool done; float* gate; };
+struct StepFin { float* kl_obj; float* kl_cost; float kl_min; bool done; float* gate; };      // (the groups: the stack's fb_groups)
 static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, const ConvP& base, int first_inmode, const float* ctx,
                              const float* ctx2, hipStream_t st, float* const* hsave = nullptr, float* kl_part = nullptr,
                              StepFin* fin = nullptr) {
@@ -1455,6 +1469,7 @@ static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, co
         if (fin_env && !(s->xch_knob & 16u))                 // (test knob 16: the finish launch, to compare against)
             if (iaf_stack::XchSet* x = xch_prepare(s, base.B, q.nrb, 0, st, f16_fn ? IAF_XSENT_F16 : IAF_XSENT)) {
                 q.fin_obj = fin->kl_obj; q.fin_cost = fin->kl_cost; q.fin_kl_min = fin->kl_min; q.fin_ctl = x->ctl + IAF_XCTL_FIN; q.fin_gate = fin->gate;
+                q.fin_groups = s->fb_groups;
                 fin->done = true;
             }
     }
@@ -1469,15 +1484,15 @@ static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, co
 // (tf_train.py:77-85): ONE 256-thread launch while one workgroup can walk the partials (B = 32: 8 k loads), a many-workgroup
 // row-block sum in front of it beyond that (config 5, B = 256).  rowsum: [B * Z] floats of scratch.
 static int launch_kl_from_parts(const float* part, float* rowsum, float* kl_obj, float* kl_cost, int B, int Z, int nrb, float kl_min,
-                                float* gate, hipStream_t st) {
+                                float* gate, int groups, hipStream_t st) {
     const long long loads = (long long)B * nrb * Z;
     if (loads <= 16384) {
-        hipLaunchKernelGGL(iaf_kl_finish_kernel, dim3(1), dim3(256), 0, st, part, kl_obj, kl_cost, B, Z, kl_min, gate, nrb, rowsum);
+        hipLaunchKernelGGL(iaf_kl_finish_kernel, dim3(1), dim3(256), 0, st, part, kl_obj, kl_cost, B, Z, kl_min, gate, nrb, rowsum, groups);
     } else {
         const int n = B * Z;
         hipLaunchKernelGGL(iaf_kl_partsum_kernel, dim3((n + 255) / 256), dim3(256), 0, st, part, rowsum, n, Z, nrb);
         hipLaunchKernelGGL(iaf_kl_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)rowsum, kl_obj, kl_cost, B, Z, kl_min, gate, 0,
-                           (float*)nullptr);
+                           (float*)nullptr, groups);
     }
     return (int)hipGetLastError();
 }
@@ -1869,6 +1884,7 @@ extern "C" int iaf_posterior_block_forward(iaf_stack_t* s, const float* qz_mean,
         !kl_cost)
         return IAF_ERR_NULL;
     if (s->depth_ar > 0 && (!up_context || !down_context)) return IAF_ERR_NULL;
+    if (B % s->fb_groups != 0) return IAF_ERR_SHAPE;
     Ws ws;
     if ((rc = carve_ws(s, B, H, W, workspace, workspace_bytes, &ws))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1890,28 +1906,28 @@ extern "C" int iaf_posterior_block_forward(iaf_stack_t* s, const float* qz_mean,
             StepFin fin = {kl_obj, kl_cost, kl_min, false, nullptr};
             if ((rc = launch_fused_step(s, fn, R, lds, p, IN_POSTERIOR, up_context, down_context, st, nullptr, ws.hbuf[0], &fin))) return rc;
             if (fin.done) return IAF_OK;                       // the launch's last workgroup did the block's reductions too
-            return launch_kl_from_parts(ws.hbuf[0], ws.rowsum, kl_obj, kl_cost, B, s->n_z, nrb, kl_min, nullptr, st);
+            return launch_kl_from_parts(ws.hbuf[0], ws.rowsum, kl_obj, kl_cost, B, s->n_z, nrb, kl_min, nullptr, s->fb_groups, st);
         }
     }
     if ((rc = run_stack(s, p, IN_POSTERIOR, up_context, down_context, ws, st))) return rc;
     const int rows = B * s->n_z;
     hipLaunchKernelGGL(iaf_kl_rowsum_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, p.kl_elem, ws.rowsum, rows, H * W);
     hipLaunchKernelGGL(iaf_kl_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)ws.rowsum, kl_obj, kl_cost, B, s->n_z, kl_min,
-                       (float*)nullptr, 0, (float*)nullptr);
+                       (float*)nullptr, 0, (float*)nullptr, s->fb_groups);
     return (int)hipGetLastError();
 }
 
 // free bits on given KL elements (tf_train.py:77-85; models.py:455-466): kl_elem [B,C,H,W] -> kl_obj [B], kl_cost [B];
 // scratch: B*C floats
 static int kl_free_bits_impl(const float* kl_elem, float* kl_obj, float* kl_cost, float* gate, int B, int C, int HW, float kl_min,
-                             float* scratch, void* stream) {
+                             float* scratch, void* stream, int groups = 1) {
     if (!kl_elem || !kl_obj || !kl_cost || !scratch) return IAF_ERR_NULL;
-    if (B <= 0 || C <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    if (B <= 0 || C <= 0 || HW <= 0 || groups < 1 || groups > IAF_MAX_FREE_BITS_GROUPS || B % groups != 0) return IAF_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int rows = B * C;
     hipLaunchKernelGGL(iaf_kl_rowsum_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, kl_elem, scratch, rows, HW);
     hipLaunchKernelGGL(iaf_kl_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)scratch, kl_obj, kl_cost, B, C, kl_min, gate,
-                       0, (float*)nullptr);
+                       0, (float*)nullptr, groups);
     return (int)hipGetLastError();
 }
 extern "C" int iaf_kl_free_bits(const float* kl_elem, float* kl_obj, float* kl_cost, int B, int C, int HW, float kl_min,
@@ -1923,6 +1939,11 @@ extern "C" int iaf_kl_free_bits_gate(const float* kl_elem, float* kl_obj, float*
                                      float kl_min, float* scratch, void* stream) {
     if (!gate) return IAF_ERR_NULL;
     return kl_free_bits_impl(kl_elem, kl_obj, kl_cost, gate, B, C, HW, kl_min, scratch, stream);
+}
+// ... with the free-bits mean per contiguous group of B / groups rows; gate [groups][C] or NULL
+extern "C" int iaf_kl_free_bits_grouped(const float* kl_elem, float* kl_obj, float* kl_cost, float* gate_or_null, int B, int C, int HW,
+                                        int groups, float kl_min, float* scratch, void* stream) {
+    return kl_free_bits_impl(kl_elem, kl_obj, kl_cost, gate_or_null, B, C, HW, kl_min, scratch, stream, groups);
 }
 
 static dim3 ew_grid(size_t n) {
@@ -2162,7 +2183,7 @@ struct TrainWs {
     // posterior block: saved forward values and backward temporaries, all NCHW [P*n_z] unless noted
     float* logsd; float* klelem; float* z0; float* dzt; float* dkl; float* dz0;
     float* rowsum;   // [B*n_z]  (P*n_z floats reserved: B <= P)
-    float* gate;     // [n_z]
+    float* gate;     // [fb_groups][n_z]
     unsigned short* tapmask;   // [P] border bits for the weight gradient
 };
 
@@ -2183,7 +2204,7 @@ static size_t train_ws_floats(const iaf_stack_t* s, long long P, TrainWs* o, flo
     t.logsd = take((size_t)P * s->n_z); t.klelem = take((size_t)P * s->n_z); t.z0 = take((size_t)P * s->n_z);
     t.dzt = take((size_t)P * s->n_z); t.dkl = take((size_t)P * s->n_z); t.dz0 = take((size_t)P * s->n_z);
     t.rowsum = take((size_t)P * s->n_z);
-    t.gate = take((size_t)s->n_z);
+    t.gate = take((size_t)s->fb_groups * s->n_z);
     t.tapmask = (unsigned short*)take(((size_t)P + 1) / 2);
     if (o) *o = t;
     return off;
@@ -2613,6 +2634,7 @@ extern "C" int iaf_posterior_block_forward_train(iaf_stack_t* s, const float* qz
         !workspace)
         return IAF_ERR_NULL;
     if (s->depth_ar > 0 && (!up_context || !down_context)) return IAF_ERR_NULL;
+    if (B % s->fb_groups != 0) return IAF_ERR_SHAPE;
     if (((uintptr_t)workspace & 15) != 0 || workspace_bytes < iaf_stack_train_workspace_bytes(s, B, H, W)) return IAF_ERR_WORKSPACE;
     TrainWs tw;
     train_ws_floats(s, (long long)B * H * W, &tw, (float*)workspace);
@@ -2633,7 +2655,7 @@ extern "C" int iaf_posterior_block_forward_train(iaf_stack_t* s, const float* qz
             StepFin fin = {kl_obj, kl_cost, kl_min, false, tw.gate};
             if ((rc = launch_fused_step(s, fn, R, lds, base, IN_POSTERIOR, up_context, down_context, st, tw.h, tw.klelem, &fin))) return rc;
             if (fin.done) return IAF_OK;
-            return launch_kl_from_parts(tw.klelem, tw.rowsum, kl_obj, kl_cost, B, s->n_z, (H + R - 1) / R, kl_min, tw.gate, st);
+            return launch_kl_from_parts(tw.klelem, tw.rowsum, kl_obj, kl_cost, B, s->n_z, (H + R - 1) / R, kl_min, tw.gate, s->fb_groups, st);
         }
     }
     if (s->generic) {
@@ -2659,7 +2681,7 @@ extern "C" int iaf_posterior_block_forward_train(iaf_stack_t* s, const float* qz
     const int rows = B * s->n_z;
     hipLaunchKernelGGL(iaf_kl_rowsum_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, tw.klelem, tw.rowsum, rows, H * W);
     hipLaunchKernelGGL(iaf_kl_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)tw.rowsum, kl_obj, kl_cost, B, s->n_z, kl_min, tw.gate, 0,
-                       (float*)nullptr);
+                       (float*)nullptr, s->fb_groups);
     return (int)hipGetLastError();
 }
 
@@ -2676,15 +2698,16 @@ extern "C" int iaf_posterior_block_backward(iaf_stack_t* s, const float* qz_mean
     if (!qz_mean || !qz_logsd || !rz_mean || !rz_logsd || !pz_mean || !pz_logsd || !eps || !z || !dkl_obj || !dmean ||
         !dlogsd_q || !dpz_mean || !dpz_logsd || !workspace)
         return IAF_ERR_NULL;
+    if (B % s->fb_groups != 0) return IAF_ERR_SHAPE;
     if (((uintptr_t)workspace & 15) != 0 || workspace_bytes < iaf_stack_train_workspace_bytes(s, B, H, W)) return IAF_ERR_WORKSPACE;
     TrainWs tw;
     train_ws_floats(s, (long long)B * H * W, &tw, (float*)workspace);
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)B * s->n_z * H * W;
-    // the free-bits gate [n_z] was left in the workspace by iaf_posterior_block_forward_train (same kl_min)
+    // the free-bits gate [groups][n_z] was left in the workspace by iaf_posterior_block_forward_train (same kl_min, same groups)
     hipLaunchKernelGGL(iaf_post_bwd_pre_kernel, ew_grid(n), dim3(256), 0, st, qz_mean, qz_logsd, rz_mean, rz_logsd, pz_mean,
                        pz_logsd, eps, z, dz, tw.gate, dkl_obj, kl_min, tw.z0, tw.dzt, tw.dkl, dpz_mean, dpz_logsd, B, s->n_z,
-                       H * W, n);
+                       H * W, n, s->fb_groups);
     if ((rc = (int)hipGetLastError())) return rc;
     // core: z := z0, (z_new, logsd) := saved forward values, incoming gradients := (dz_tot, dkl)
     if ((rc = iaf_step_backward(s, tw.z0, dcontext /* value unused */, z, tw.logsd, tw.dzt, tw.dkl, tw.dz0, dcontext, V, g, dV, dg,

@@ -809,7 +809,8 @@ __global__ __launch_bounds__(256) void iaf_wn_bwd_plain_batch_kernel(const WnBwd
 
 // (4) posterior block backward, elementwise parts (tf_train.py:56-85 differentiated):
 //   pre : dkl[b,c,:,:] = G[b,c]  (free bits: G = gate[c] (sum_b' dkl_obj[b']) / B, gate = [mean_b S[b,c] > kl_min];
-//                                  kl_min <= 0: G = dkl_obj[b]);
+//                                  kl_min <= 0: G = dkl_obj[b]; groups > 1: gate [groups][Z], the sum and the mean over
+//                                  the rows of b's group, a contiguous run of B / groups rows);
 //         z0 = mean + e^{lq} eps;  d z_tot = dz + dkl (z - pm) e^{-2 pl};  d pm = -dkl (z - pm) e^{-2 pl};
 //         d pl = dkl (1 - (z - pm)^2 e^{-2 pl});   core inputs: dz_new := dz_tot, dlogsd := dkl  (logqs += s)
 //   post: d mean = dz0;  d lq = dz0 (z0 - mean) - dkl     (d logq0/d mean = 0 and d logq0/d lq = -1 after the
@@ -820,10 +821,21 @@ __global__ __launch_bounds__(256) void iaf_post_bwd_pre_kernel(const float* qm, 
                                                               const float* pm, const float* pl, const float* eps, const float* z,
                                                               const float* dz, const float* gate, const float* dkl_obj, float kl_min,
                                                               float* z0, float* dzt, float* dkl, float* dpm, float* dpl, int B, int Z,
-                                                              int HW, size_t n) {
+                                                              int HW, size_t n, int groups) {
     __shared__ float s_part[4];
+    __shared__ float s_gsum[64];
     float gsum = 0.f;
-    if (kl_min > 0.f) {
+    const int GR = B / groups;
+    if (kl_min > 0.f && groups > 1) {
+        // one wave per group in turn: the group's rows over the lanes, then the shuffle tree
+        for (int r = threadIdx.x >> 6; r < groups; r += 4) {
+            float a = 0.f;
+            for (int b = threadIdx.x & 63; b < GR; b += 64) a += dkl_obj[(size_t)r * GR + b];
+            for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
+            if ((threadIdx.x & 63) == 0) s_gsum[r] = a / (float)GR;
+        }
+        __syncthreads();
+    } else if (kl_min > 0.f) {
         float a = 0.f;
         for (int b = threadIdx.x; b < B; b += 256) a += dkl_obj[b];
         for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
@@ -835,7 +847,13 @@ __global__ __launch_bounds__(256) void iaf_post_bwd_pre_kernel(const float* qm, 
         const size_t bc = i / HW;
         const int c = (int)(bc % Z);
         const size_t b = bc / Z;
-        const float g = (kl_min > 0.f) ? gate[c] * gsum : dkl_obj[b];
+        float g;
+        if (groups > 1 && kl_min > 0.f) {
+            const int r = (int)(b / (size_t)GR);
+            g = gate[(size_t)r * Z + c] * s_gsum[r];
+        } else {
+            g = (kl_min > 0.f) ? gate[c] * gsum : dkl_obj[b];
+        }
         const float mean = qm[i] + rm[i], lq = ql[i] + rl[i];
         z0[i] = mean + __expf(0.5f * (2.f * lq)) * eps[i];
         const float e2 = __expf(-2.f * pl[i]);

@@ -22,13 +22,16 @@ __global__ __launch_bounds__(256) void iaf_kl_rowsum_kernel(const float* kl, flo
 // nrb > 0: S holds per-row-block partial sums [B][nrb][Z] (the one-launch step's StepP::kl_part) and the sum over the row
 // blocks -- in row order, eight loads in flight -- is the first thing this launch does; nrb = 0: S is [B][Z].
 // scratch ([B*Z] floats) is only touched when B*Z does not fit the LDS staging.
+// groups (1 .. 64, B % groups == 0): the free-bits mean is taken per contiguous run of G = B / groups rows (one tower of the
+// reference's multi-tower step each, tf_train.py:126) -- a group's numbers are what a stand-alone G-row batch gives, its rows
+// summed in row order, so groups = 1 is the one-batch arithmetic bit for bit; gate is then [groups][Z].
 __global__ __launch_bounds__(256) void iaf_kl_finish_kernel(const float* S, float* kl_obj, float* kl_cost, int B, int Z,
-                                                           float kl_min, float* gate, int nrb, float* scratch) {
+                                                           float kl_min, float* gate, int nrb, float* scratch, int groups) {
     // S is tiny ([B, Z]); stage it through LDS in one coalesced sweep instead of B*Z dependent global loads
     __shared__ float sh[8192];
     __shared__ float part[256];
-    __shared__ float s_fb;
-    const int tid = threadIdx.x, n = B * Z;
+    __shared__ float s_fb[64];
+    const int tid = threadIdx.x, n = B * Z, G = B / groups;
     const bool in_lds = n <= 8192;
     if (nrb > 0) {
         // item = four consecutive channels of one image: its nrb partial sums are nrb independent 16-byte loads, eight in
@@ -69,27 +72,30 @@ __global__ __launch_bounds__(256) void iaf_kl_finish_kernel(const float* S, floa
     const float* src = in_lds ? sh : (nrb > 0 ? scratch : S);
     if (kl_min > 0.f) {
         // kl_ave[c] = max(mean_b S[b,c], kl_min); kl_obj[b] = sum_c kl_ave[c]   (tf_train.py:79-82)
-        float a = 0.f;
-        for (int c = tid; c < Z; c += 256) {
-            float m = 0.f;
-            for (int b = 0; b < B; ++b) m += src[(size_t)b * Z + c];
-            a += fmaxf(m / (float)B, kl_min);
-            if (gate) gate[c] = (m / (float)B > kl_min) ? 1.f : 0.f;
-        }
-        part[tid] = a;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) part[tid] += part[tid + o];
+        for (int r = 0; r < groups; ++r) {
+            const float* sg = src + (size_t)r * G * Z;
+            float a = 0.f;
+            for (int c = tid; c < Z; c += 256) {
+                float m = 0.f;
+                for (int b = 0; b < G; ++b) m += sg[(size_t)b * Z + c];
+                a += fmaxf(m / (float)G, kl_min);
+                if (gate) gate[(size_t)r * Z + c] = (m / (float)G > kl_min) ? 1.f : 0.f;
+            }
+            part[tid] = a;
+            __syncthreads();
+            for (int o = 128; o > 0; o >>= 1) {
+                if (tid < o) part[tid] += part[tid + o];
+                __syncthreads();
+            }
+            if (tid == 0) s_fb[r] = part[0];
             __syncthreads();
         }
-        if (tid == 0) s_fb = part[0];
-        __syncthreads();
     }
     for (int b = tid; b < B; b += 256) {
         float a = 0.f;
         for (int c = 0; c < Z; ++c) a += src[(size_t)b * Z + c];
         kl_cost[b] = a;                                        // tf_train.py:85
-        kl_obj[b] = (kl_min > 0.f) ? s_fb : a;                 // tf_train.py:82 / 84
+        kl_obj[b] = (kl_min > 0.f) ? s_fb[b / G] : a;          // tf_train.py:82 / 84
     }
 }
 

@@ -1342,21 +1342,32 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                 }
                 __syncthreads();
                 if (htid < 64) {                                  // one wave: n_z <= 64 channels, then B images in rounds of 64
-                    float a = 0.f;
-                    if (htid < NZ) {
-                        float m = 0.f;
-                        for (int bb = 0; bb < p.B; ++bb) m += S[(size_t)bb * NZ + htid];
-                        a = fmaxf(m / (float)p.B, p.fin_kl_min);  // kl_ave[c] = max(mean_b S[b,c], kl_min)          (tf_train.py:79-80)
-                        if (p.fin_gate && p.fin_kl_min > 0.f) p.fin_gate[htid] = (m / (float)p.B > p.fin_kl_min) ? 1.f : 0.f;
-                    }
+                    // per group of GR = B / fin_groups rows (one group: the whole batch); lane r keeps group r's clamped sum
+                    const int GR = p.B / p.fin_groups;
+                    float fbv = 0.f;
+                    for (int g = 0; g < p.fin_groups; ++g) {
+                        float a = 0.f;
+                        if (htid < NZ) {
+                            const float* Sg = S + (size_t)g * GR * NZ;
+                            float m = 0.f;
+                            for (int bb = 0; bb < GR; ++bb) m += Sg[(size_t)bb * NZ + htid];
+                            a = fmaxf(m / (float)GR, p.fin_kl_min);   // kl_ave[c] = max(mean_b S[b,c], kl_min)      (tf_train.py:79-80)
+                            if (p.fin_gate && p.fin_kl_min > 0.f) p.fin_gate[g * NZ + htid] = (m / (float)GR > p.fin_kl_min) ? 1.f : 0.f;
+                        }
 #pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);      // (the finish kernel's tree: part[t] += part[t + o])
-                    const float fb = __shfl(a, 0, 64);
-                    for (int bb = htid; bb < p.B; bb += 64) {
-                        float c = 0.f;
-                        for (int cc = 0; cc < NZ; ++cc) c += S[(size_t)bb * NZ + cc];
-                        p.fin_cost[bb] = c;                                           // tf_train.py:85
-                        p.fin_obj[bb] = p.fin_kl_min > 0.f ? fb : c;                  // tf_train.py:82 / 84
+                        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);  // (the finish kernel's tree: part[t] += part[t + o])
+                        const float fb = __shfl(a, 0, 64);
+                        if (htid == g) fbv = fb;
+                    }
+                    for (int b0 = 0; b0 < p.B; b0 += 64) {        // (every lane takes part in the shuffle)
+                        const int bb = b0 + htid;
+                        const float fb = __shfl(fbv, bb < p.B ? bb / GR : 0, 64);
+                        if (bb < p.B) {
+                            float c = 0.f;
+                            for (int cc = 0; cc < NZ; ++cc) c += S[(size_t)bb * NZ + cc];
+                            p.fin_cost[bb] = c;                                       // tf_train.py:85
+                            p.fin_obj[bb] = p.fin_kl_min > 0.f ? fb : c;              // tf_train.py:82 / 84
+                        }
                     }
                 }
             }

@@ -30,12 +30,14 @@ struct StepP {
     // iaf_kl_finish_kernel behind the launch): the LAST workgroup to arrive -- counted in fin_ctl, 64-bit words, one 128-byte line
     // each: [32 g] arrivals of the workgroups with blockIdx % 8 = g, [256] groups complete; zero between launches -- sums kl_part
     // over the row blocks, takes the batch mean / max(., kl_min) / channel sum (tf_train.py:79-85) and writes fin_obj, fin_cost [B],
-    // in the summation order of iaf_kl_finish_kernel (bit-identical results).
+    // in the summation order of iaf_kl_finish_kernel (bit-identical results).  fin_groups (1 .. 64, divides B): the batch mean per
+    // contiguous run of B / fin_groups rows, as that kernel's `groups`; fin_gate is then [fin_groups][n_z].
     float* fin_obj;
     float* fin_cost;
     float* fin_gate;               // optional [n_z]: 1 where the free-bits max() passes the gradient (training forward), else 0
     unsigned long long* fin_ctl;
     float fin_kl_min;
+    int fin_groups;
     // XCH kernels (halo rows exchanged between the row blocks of an image instead of recomputed; iaf_step_fused.hpp "XCH"):
     char* xh;                      // rows [layer][B * nrb][xrow bytes]; every dword = IAF_XSENT between launches (the data is the flag)
                                    // (PAIR kernels: [B * nrb][half][prow bytes], the halves of the last hidden region the partners swap)

@@ -69,6 +69,14 @@ class IAFLayer(object):
         self.down_conv1 = WNConv2d(hs, 4 * zs + 2 * hs)    # :53
         self.down_conv2 = WNConv2d(hs + zs, hs)            # :93 (down_deconv2, :91, when downsampling)
         self.posterior = IAFPosterior(zs, hs, depth_ar, kl_min)
+        self.towers = 1
+
+    def set_towers(self, n=1):
+        """n towers of the reference's training step in one batch (tf_train.py:124-147): rows t B/n .. (t+1) B/n are tower t, and the free-bits
+        mean of down() / down_train() / down_backward() is taken per tower (ARStack.set_free_bits_groups); everything else in the layer is
+        per row.  1 (the default): one free-bits mean over the batch."""
+        self.posterior.stack.set_free_bits_groups(n)
+        self.towers = n
 
     @property
     def last_conv_name(self):

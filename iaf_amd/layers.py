@@ -312,6 +312,19 @@ class ARStack(object):
         """False: the one-launch step of this stack recomputes its halo rows instead of exchanging them (include/iaf_hip.h)"""
         _capi.check(_capi.lib().iaf_stack_set_halo_exchange(self._h, 1 if on else 0))
 
+    def set_free_bits_groups(self, n=1):
+        """The free-bits mean of posterior_block / posterior_block_train / posterior_block_backward per contiguous group of B / n rows
+        instead of over the whole batch: the n towers of the reference's training step (tf_train.py:79-82, 124-147) as one pass over
+        n * batch_size rows.  kl_obj[b] becomes its group's clamped sum, kl_cost is unchanged, B must be a multiple of n.  1 (the default)
+        is the one-batch statement.  A posterior_block_train / posterior_block_backward pair must see the same value.  TF statement only
+        (UnsupportedError for the Theano variants with n > 1).  See include/iaf_hip.h, iaf_stack_set_free_bits_groups."""
+        _capi.check(_capi.lib().iaf_stack_set_free_bits_groups(self._h, check_groups(n, "groups")))
+
+    def free_bits_groups(self):
+        n = ctypes.c_int(0)
+        _capi.check(_capi.lib().iaf_stack_get_free_bits_groups(self._h, ctypes.byref(n)))
+        return int(n.value)
+
     def set_halo_exchange_debug(self, knobs=0):
         """test knobs of the exchange (include/iaf_hip.h: 1 lists ignore the placement, 2 tickets out of dispatch order,
         8 fault injection); 0 = production"""
@@ -929,14 +942,31 @@ def split(x, split_dim, split_sizes):
     return out
 
 
-def kl_free_bits(kl, kl_min, want_gate=False):
+MAX_FREE_BITS_GROUPS = 64       # IAF_MAX_FREE_BITS_GROUPS (include/iaf_hip.h)
+
+
+def check_groups(n, what="groups"):
+    """a number of free-bits row groups / towers: an int (no bool) in 1 .. MAX_FREE_BITS_GROUPS"""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_FREE_BITS_GROUPS:
+        raise ValueError("%s must be an int in 1 .. %d, got %r" % (what, MAX_FREE_BITS_GROUPS, n))
+    return n
+
+
+def kl_free_bits(kl, kl_min, want_gate=False, groups=1):
     """[B, C, H, W] KL elements -> (kl_cost [B], kl_obj [B]) (tf_train.py:77-85) with the engine's reduction kernels;
-    want_gate: also the per-channel gate [C] of the free bits (1 where the batch mean of the channel's KL exceeds kl_min)"""
+    want_gate: also the per-channel gate [C] of the free bits (1 where the batch mean of the channel's KL exceeds kl_min).
+    groups > 1: the batch mean per contiguous group of B / groups rows (ARStack.set_free_bits_groups); the gate is then [groups, C]."""
+    check_groups(groups)
     _check_act(kl, "kl")
     B, C, H, W = (int(v) for v in kl.shape)
     kl_obj = torch.empty(B, dtype=torch.float32, device=kl.device)
     kl_cost = torch.empty_like(kl_obj)
     scratch = torch.empty(B * C, dtype=torch.float32, device=kl.device)
+    if groups != 1:
+        gate = torch.empty(groups, C, dtype=torch.float32, device=kl.device) if want_gate else None
+        _capi.check(_capi.lib().iaf_kl_free_bits_grouped(_ptr(kl), _ptr(kl_obj), _ptr(kl_cost), _ptr(gate), B, C, H * W, groups,
+                                                         float(kl_min), _ptr(scratch), _stream()))
+        return (kl_cost, kl_obj, gate) if want_gate else (kl_cost, kl_obj)
     if want_gate:
         gate = torch.empty(C, dtype=torch.float32, device=kl.device)
         _capi.check(_capi.lib().iaf_kl_free_bits_gate(_ptr(kl), _ptr(kl_obj), _ptr(kl_cost), _ptr(gate), B, C, H * W, float(kl_min),

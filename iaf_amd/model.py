@@ -12,16 +12,26 @@ import torch
 from . import _capi
 from .distributions import StreamingLowerBound, compute_lowerbound, discretized_logistic
 from .iaf_layer import IAFLayer
-from .layers import (ConvPrepBatch, PrepBatch, VariableStore, WnBwdBatch, ar_multiconv2d, resample2, variable_scope, _check_act, _ptr,
+from .layers import (check_groups, ConvPrepBatch, PrepBatch, VariableStore, WnBwdBatch, ar_multiconv2d, resample2, variable_scope, _check_act, _ptr,
                      _stream)
 
 
 class CVAE1(object):
     """Same hyper-parameters as the reference's HParams (tf_train.py:98-112) that _forward reads: z_size, h_size, kl_min, depth
     (number of resolution levels), num_blocks (layers per level), k (importance samples), image_size.  `mode` as in the
-    reference: "train" (posterior samples), "init" (prior samples through the posterior block), "sample"."""
+    reference: "train" (posterior samples), "init" (prior samples through the posterior block), "sample".
 
-    def __init__(self, z_size=32, h_size=160, kl_min=0.25, depth=2, num_blocks=2, k=1, image_size=32, depth_ar=2, mode="train"):
+    towers=N (1 .. 64, attribute model.towers): the N towers of the reference's training step (tf_train.py:124-147, num_gpus) in ONE batch.
+    Rows t B/N .. (t+1) B/N of x and of every noise tensor are tower t (tf.split(0, num_gpus, x), :126); every layer takes its free-bits
+    mean per tower (:79-82, the only place where rows of a batch meet), so obj and loss are the sums over the towers of what the
+    reference's _forward returns for each, and the gradients the sums over the towers (average_grads' sum; TrainStep divides by
+    world * towers).  forward, forward_backward, fb_begin / fb_segment and TrainStep need nothing else; B must be a multiple of N.
+    generate, sample, iw_eval (it reads kl_cost only; its B too is a multiple of N) and init_pass (the reference initialises on one
+    tower's batch: any B) are unaffected.
+    1 (the default): one free-bits mean over the whole batch, as before."""
+
+    def __init__(self, z_size=32, h_size=160, kl_min=0.25, depth=2, num_blocks=2, k=1, image_size=32, depth_ar=2, mode="train", towers=1):
+        self.towers = check_groups(towers, "towers")
         self.z_size, self.h_size, self.kl_min = int(z_size), int(h_size), float(kl_min)
         self.depth, self.num_blocks, self.k, self.image_size, self.mode = int(depth), int(num_blocks), int(k), int(image_size), mode
         self.depth_ar = int(depth_ar)
@@ -30,6 +40,10 @@ class CVAE1(object):
         # tf_train.py:176-181: the first layer of every level but the first downsamples
         self.layers = [[IAFLayer(z_size, h_size, depth_ar=depth_ar, kl_min=kl_min, downsample=(i > 0 and j == 0), mode=mode)
                         for j in range(self.num_blocks)] for i in range(self.depth)]
+        if self.towers != 1:
+            for level in self.layers:
+                for layer in level:
+                    layer.set_towers(self.towers)
         self._w_enc = self._w_dec = None
         self.params = None
 
@@ -299,6 +313,8 @@ class CVAE1(object):
         B, _, S, S2 = (int(v) for v in x.shape)
         if S != self.image_size or S2 != S:
             raise ValueError("image size %r, model built for %d" % (tuple(x.shape), self.image_size))
+        if k is not None and B % self.towers:            # (init_pass, k None: one tower's batch, no free bits)
+            raise ValueError("batch of %d rows, model built for %d towers: B must be a multiple of towers" % (B, self.towers))
         if len(noise) != 2 * self.depth * self.num_blocks:
             raise ValueError("noise: %d tensors expected (prior, posterior per layer, top-down)" % (2 * self.depth * self.num_blocks))
         n = B * (self.k if k is None else k)

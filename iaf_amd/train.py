@@ -6,7 +6,7 @@ The step is the one bench.py --train --model times: every weight norm re-derived
 all-reduce(sum) issued behind backward segment i (parallel.OverlappedGradReduce), the join, then
   - the guard scan (iaf_nonfinite_scan) of the reduced flat gradient and of a status word that went through the same reduce (the
     sum of the ranks' objectives: one rank's non-finite objective makes it non-finite on every rank), and
-  - the gated Adamax / EMA (iaf_adamax_ema_step_guarded, grad_scale 1/world): bit-identical to FlatParams.adamax_ema_step when
+  - the gated Adamax / EMA (iaf_adamax_ema_step_guarded, grad_scale 1/world; 1/(world * towers) for a model with towers): bit-identical to FlatParams.adamax_ema_step when
     the guard is clear; when it is raised nothing moves and a counter in mapped host memory counts the skip.
 Every rank scans the same reduced numbers, so every rank takes the same decision.  A skipped batch is dropped (as
 torch.amp.GradScaler does), not recomputed.
@@ -27,6 +27,7 @@ import torch
 import torch.distributed as dist
 
 from . import _capi
+from .layers import check_groups
 from .parallel import FlatParams, OverlappedGradReduce
 
 # the errors an object reports once, at its next eager call, about an EARLIER launch whose outputs carry inf / NaN; the object has
@@ -97,7 +98,12 @@ class TrainStep(object):
     ts.summaries(reset=True) synchronises and returns the means over the accepted steps since the last reset (NaN when there were
     none) under the reference's tags -- model/bits_per_dim, model/dec_log_stdv, model/log_pxz, model/kl_obj, model/kl_cost,
     model/kl_obj_%02d_%02d, model/kl_cost_%02d_%02d -- plus grad_norm (the norm of the averaged gradient), steps and skipped;
-    ts.last_summaries() the same keys for the most recent step alone, accepted or not."""
+    ts.last_summaries() the same keys for the most recent step alone, accepted or not.
+
+    A model with towers (model.towers = N > 1, CVAE1(towers=N)): this rank's batch holds N of the reference's towers, so the update and
+    grad_norm use 1/(world * N) where they use 1/world otherwise (average_grads over all towers); model/bits_per_dim already counts every
+    row (tf_train.py:142).  Deviation: the reference logs its KL and log_pxz summaries from the LAST tower only (tf_train.py:202, 213);
+    here they are means over all rows."""
 
     _FIXED = ("model/bits_per_dim", "model/dec_log_stdv", "model/log_pxz", "model/kl_obj", "model/kl_cost", "grad_norm")
 
@@ -147,6 +153,10 @@ class TrainStep(object):
         self.world = 1
         if self.red.active:
             self.world = int(getattr(self.red.comm, "world", 0) or dist.get_world_size())
+        # the reference's towers inside this rank's batch (CVAE1(towers=N), tf_train.py:124-147): the gradients are sums over world * towers
+        # towers, which average_grads divides by their number
+        self.towers = check_groups(getattr(model, "towers", 1), "model.towers")
+        self._replicas = self.world * self.towers
         dev = self.flat.params.device
         # [0]: the step's objective, summed over the ranks by the same exchange as the gradients (the rest: 16-byte padding)
         self._status = torch.zeros(4, dtype=torch.float32, device=dev)
@@ -256,7 +266,7 @@ class TrainStep(object):
         """the record's fields of this step with torch fp64 ops (host replicas)"""
         t, f64 = self._terms, torch.float64
         lo, lc = t["layer_obj"].to(f64).mean(dim=1), t["layer_cost"].to(f64).mean(dim=1)
-        norm = (1.0 / self.world) * torch.sqrt((self.flat.grads.to(f64) ** 2).sum())
+        norm = (1.0 / self._replicas) * torch.sqrt((self.flat.grads.to(f64) ** 2).sum())
         head = [self._status[1].to(f64), self.model.params["dec_log_stdv"].reshape(-1)[0].to(f64), -t["log_pxz"].to(f64).mean(), lo.sum(),
                 lc.sum(), norm]
         return torch.cat([torch.stack(head), torch.stack([lo, lc], dim=1).reshape(-1)])
@@ -274,12 +284,12 @@ class TrainStep(object):
                                                          ptr(self._partials), ptr(self._sumsq), st))
                 _capi.check(lib.iaf_train_summaries(ptr(t["layer_obj"]), ptr(t["layer_cost"]), ptr(t["log_pxz"]),
                                                     ptr(self.model.params["dec_log_stdv"]), ctypes.c_void_p(self._status.data_ptr() + 4),
-                                                    ptr(self._sumsq), 1.0 / self.world, ptr(self._guard), ptr(self._rec), nl, n, st))
+                                                    ptr(self._sumsq), 1.0 / self._replicas, ptr(self._guard), ptr(self._rec), nl, n, st))
             else:
                 _capi.check(lib.iaf_nonfinite_scan(ptr(flat.grads), flat.grads.numel(), ptr(self._status), 1, ptr(self._guard), st))
             _capi.check(lib.iaf_adamax_ema_step_guarded(ptr(flat.params), ptr(flat.grads), ptr(flat.slot_m), ptr(flat.slot_v),
                                                         ptr(flat.ema), flat.params.numel(), self.lr, b1, b2, eps, decay,
-                                                        1.0 / self.world, ptr(self._guard), self._skips._h, st))
+                                                        1.0 / self._replicas, ptr(self._guard), self._skips._h, st))
             # (raw-pointer writes: tell torch, as FlatParams.adamax_ema_step does)
             torch.autograd.graph.increment_version((flat.params, flat.ema, flat.slot_m, flat.slot_v))
         else:        # host replicas: the same decision with torch ops
@@ -293,7 +303,7 @@ class TrainStep(object):
                 else:
                     rec["skipped"] += 1
             if ok:
-                flat.adamax_ema_step(self.lr, world=self.world, beta1=b1, beta2=b2, eps=eps, ema_decay=decay)
+                flat.adamax_ema_step(self.lr, world=self._replicas, beta1=b1, beta2=b2, eps=eps, ema_decay=decay)
             else:
                 self._host_skips += 1
 

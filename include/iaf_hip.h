@@ -180,6 +180,24 @@ int iaf_posterior_block_backward(iaf_stack_t* s, const float* qz_mean, const flo
                                  float* const* db, int B, int H, int W, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* Free bits per row group: the N towers of the reference's training step (tf_train.py:124-147: batch_size rows per tower,
+ * gradients summed over the towers and divided by N) as ONE pass over N * batch_size rows.  Each tower takes its free-bits
+ * mean over its own rows (tf_train.py:79-82), the only place where rows of a batch meet; everything else is per row, and
+ * the weight-gradient kernels sum over all rows, which is average_grads' sum over the towers (the 1/N rides in
+ * iaf_adamax_ema_step's grad_scale).  After iaf_stack_set_free_bits_groups(s, groups), iaf_posterior_block_forward,
+ * iaf_posterior_block_forward_train and iaf_posterior_block_backward partition their B rows into `groups` equal contiguous
+ * runs of G = B / groups rows (IAF_ERR_SHAPE if B % groups != 0) and, with kl_min > 0, for row b of group r
+ *     kl_obj[b] = sum_c max(mean_{b' in r} S[b', c], kl_min),     S[b, c] = sum_hw kl[b, c, :, :];
+ * kl_cost is unchanged.  A group's numbers are those of a stand-alone G-row call.  The gate in the training workspace becomes
+ * [groups][n_z]: iaf_stack_train_workspace_bytes grows by (groups - 1) * n_z floats (rounded up to the carve's 64-float
+ * granularity) when groups > 1, so query it after this call.  A forward_train / backward pair must see the same value.
+ * 1 <= groups <= IAF_MAX_FREE_BITS_GROUPS, else IAF_ERR_SHAPE; groups = 1 (the default) is the one-batch statement: every
+ * launch, every result bit and every workspace size as before.  The Theano variants return IAF_ERR_UNSUPPORTED for
+ * groups > 1 (their objective is one scalar per layer, models.py:458-461). */
+#define IAF_MAX_FREE_BITS_GROUPS 64
+int iaf_stack_set_free_bits_groups(iaf_stack_t* s, int groups);
+int iaf_stack_get_free_bits_groups(const iaf_stack_t* s, int* groups);
+
 /* The gradient exchange of a data-parallel training step: all-reduce(sum) over the ranks' flat fp32 gradient buffers
  * (tf_utils/common.py:83-86, average_grads: per-variable sum over the towers of tf_train.py:124-147, then 1/N -- the 1/N
  * rides in iaf_adamax_ema_step's grad_scale).  One process per GPU; RCCL (ncclAllReduce) over xGMI, bound at run time
@@ -303,6 +321,11 @@ int iaf_kl_free_bits(const float* kl_elem, float* kl_obj, float* kl_cost, int B,
  * gradient, tf_train.py:79-80 / models.py:460-461), else 0 */
 int iaf_kl_free_bits_gate(const float* kl_elem, float* kl_obj, float* kl_cost, float* gate, int B, int C, int HW, float kl_min,
                           float* scratch, void* stream);
+/* ... with the free-bits mean per contiguous group of G = B / groups rows (iaf_stack_set_free_bits_groups above): the same
+ * two launches; gate_or_null [groups][C] or NULL; groups = 1 gives the outputs of the two calls above bit for bit.
+ * IAF_ERR_SHAPE unless 1 <= groups <= IAF_MAX_FREE_BITS_GROUPS and B % groups == 0. */
+int iaf_kl_free_bits_grouped(const float* kl_elem, float* kl_obj, float* kl_cost, float* gate_or_null, int B, int C, int HW,
+                             int groups, float kl_min, float* scratch, void* stream);
 /* The elementwise halves of the backward of the Theano layer's 'up_iaf2_nl' posterior (models.py:168-176, 201-210, 295-298,
  * 454-466) on either side of iaf_step_backward.  kl = logq0 + logdet - logp(z); G = d obj / d kl = gate[c] * gscale (free bits;
  * gate from iaf_kl_free_bits_gate) or dko[b] (gate = NULL).  d_h, d_up: [B, n_h + n_z, HW] in concat([h_det, z]) order, d_up

@@ -14,6 +14,12 @@ alternation with the guarded replay (summaries_ms against guarded_alt_ms), and i
 iaf_nonfinite_scan on the same gradient buffer (fused_scan_us against scan_alt_us), then reads the record once.  The second model
 and its flat state (parameters, gradients, slots, EMA) live next to the first in the same process: about 1.3 GB more device memory at
 the default geometry.  It replays the TrainStep's private graph (ts._graph) to time the step without the input copies.
+--towers N (N > 1; --batch is then the rows PER TOWER, the reference's 16) measures instead what CVAE1(towers=N) is for, three unguarded
+steps (prep, forward, backward, Adamax / EMA with 1/N) captured as hipGraphs on one stream and replayed in alternation:
+  towers      (a) ONE pass over N * batch rows with the free-bits mean per tower (towers = N)
+  passes      (b) N passes of `batch` rows each on a towers = 1 model, their gradients accumulated with iaf_axpby
+  one_batch   (c) one pass over N * batch rows with towers = 1 (a different objective: what grouping costs)
+(a) / (b) is the feature's value, (a) / (c) its price.  Three models live side by side.
 Prints one JSON line."""
 import argparse
 import ctypes
@@ -41,6 +47,116 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def towers_main(args):
+    import torch
+    import golden_inputs as gi
+    import iaf_amd
+    from iaf_amd import _capi
+    from iaf_amd import parallel as par
+    N, B, zs, hs, nb = args.towers, args.batch, 32, 160, args.num_blocks
+    rows = N * B
+    gi.MODEL_CASES["train_step_bench"] = (rows, 1, zs, hs, 2, nb, 32, 0.25)
+    c = gi.model_case_inputs("train_step_bench")
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    rng = np.random.RandomState(99)
+    x = torch.from_numpy(rng.randint(0, 256, size=(rows, 3, 32, 32)).astype(np.uint8)).cuda()
+    noise = [dev(rng.standard_normal(e.shape)) for e in c["noise"]]
+    xs = [x[t * B:(t + 1) * B].contiguous() for t in range(N)]
+    ns = [[e[t * B:(t + 1) * B].contiguous() for e in noise] for t in range(N)]
+    lr = 1e-4
+    lib = _capi.lib()
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def build(towers):
+        m = iaf_amd.CVAE1(z_size=zs, h_size=hs, kl_min=0.25, depth=2, num_blocks=nb, k=1, image_size=32, towers=towers)
+        m.set_training(True)
+        m.load({k: dev(v) for k, v in c["params"].items()})
+        f = par.FlatParams({k: m.params[k] for k in m.completion_order()})
+        m.load(f.p)
+        nbk = len(m.set_grad_buckets(1))
+        return m, f, nbk
+
+    def fb(m, f, nbk, xx, nn, tune=False):
+        out = m.fb_begin(xx, nn, grads=f.g, autotune=tune)
+        for i in range(nbk):
+            m.fb_segment(i)
+        return out
+
+    ma_, fa, ka = build(N)
+    mb_, fb_, kb = build(1)
+    mc_, fc, kc = build(1)
+    acc = torch.zeros_like(fb_.grads)
+
+    def step_a():
+        ma_.prepare_weights()
+        fb(ma_, fa, ka, x, noise)
+        fa.adamax_ema_step(lr, world=N)
+
+    def step_b():
+        mb_.prepare_weights()
+        for t in range(N):
+            fb(mb_, fb_, kb, xs[t], ns[t])
+            dst = fb_.grads if t == N - 1 else acc                  # acc = g (+ acc); the last sum lands where the update reads it
+            _capi.check(lib.iaf_axpby(P(fb_.grads), 1.0, P(acc), 0.0 if t == 0 else 1.0, P(dst), acc.numel(), st()))
+        fb_.adamax_ema_step(lr, world=N)
+
+    def step_c():
+        mc_.prepare_weights()
+        fb(mc_, fc, kc, x, noise)
+        fc.adamax_ema_step(lr, world=1)
+
+    for tune in (True, False):                          # launch-shape search of the plain convs at both batch sizes
+        for m, f, k, xx, nn in ((ma_, fa, ka, x, noise), (mb_, fb_, kb, xs[0], ns[0]), (mc_, fc, kc, x, noise)):
+            m.prepare_weights()
+            fb(m, f, k, xx, nn, tune)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    graphs = []
+    with torch.cuda.stream(s):
+        for fn in (step_a, step_b, step_c):
+            fn()                                        # warm up on the capture stream (the exchange sets are per stream)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
+                fn()
+            graphs.append(g)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    for _ in range(3):
+        for g in graphs:
+            g.replay()
+    ta, tb, tc = [], [], []
+    for _ in range(args.rounds):
+        ta.append(timed(graphs[0].replay, args.reps))
+        tb.append(timed(graphs[1].replay, args.reps))
+        tc.append(timed(graphs[2].replay, args.reps))
+    a, b, cc = float(np.median(ta)), float(np.median(tb)), float(np.median(tc))
+    # the accumulated gradient of (b) is the one-pass gradient of (a), fp32 round-off of the sums apart (same weights only before the
+    # first update: compared on a fresh eager pass of each with the parameters of (a))
+    fb_.params.copy_(fa.params)
+    mb_.prepare_weights()
+    ma_.prepare_weights()
+    step_grad = fb(ma_, fa, ka, x, noise)
+    ga = fa.grads.clone()
+    for t in range(N):
+        fb(mb_, fb_, kb, xs[t], ns[t])
+        if t == 0:
+            acc.copy_(fb_.grads)
+        else:
+            acc.add_(fb_.grads)
+    torch.cuda.synchronize()
+    rel = float((ga - acc).abs().max() / ga.abs().max())
+    print(json.dumps({
+        "tool": "train_step_bench --towers", "towers": N, "rows_per_tower": B, "rows": rows, "z": zs, "h": hs, "depths": [nb, nb],
+        "towers_ms": a, "passes_ms": b, "one_batch_ms": cc, "towers_over_passes": a / b, "towers_over_one_batch": a / cc,
+        "towers_repeats_ms": ta, "passes_repeats_ms": tb, "one_batch_repeats_ms": tc,
+        "towers_spread": (max(ta) - min(ta)) / a, "passes_spread": (max(tb) - min(tb)) / b, "one_batch_spread": (max(tc) - min(tc)) / cc,
+        "grad_towers_vs_accumulated_rel": rel, "obj_towers": float(step_grad["obj"].item()),
+        "timing": "median of %d rounds of %d back-to-back graph replays between HIP events, the three steps in alternation" % (args.rounds, args.reps)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -48,7 +164,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--summaries", action="store_true", help="also time the step and the scan with training summaries")
+    ap.add_argument("--towers", type=int, default=1, help="N > 1: time towers = N against N passes and against one batch (see above)")
     args = ap.parse_args()
+    if args.towers > 1:
+        return towers_main(args)
     import torch
     import golden_inputs as gi
     import iaf_amd
