@@ -8,11 +8,11 @@
 // Same implicit-GEMM kernel as the masked stack with all 9 taps live (template NTP = 9) and the EPI_PLAIN epilogue:
 // ELU / channel concat fused into the input staging, channel split / residual fused into the store.
 // ---------------------------------------------------------------------------------------------
-struct iaf_conv3x3 {
+struct iaf_conv3x3 : PackState {   // precision, packs (iaf_conv3x3_set_packs), f16_off, prepared: iaf_pack_state.hpp
     int n_in, n_out;
     int mask_mode;     // 0 plain conv2d, 1 ar_conv2d(zerodiagonal=False), 2 ar_conv2d(zerodiagonal=True)
     int variant = IAF_VARIANT_TF;   // masked convs only: the Theano statements of ar.conv2d (graphy/nodes/ar.py:200-375)
-    bool generic, prepared;
+    bool generic;
     GemmLayer L;
     PrepLayer* h_desc = nullptr;   // pinned staging of the prep descriptor
     PrepLayer* d_desc = nullptr;
@@ -22,11 +22,7 @@ struct iaf_conv3x3 {
     // IAF_PRECISION_F16X2 (round 6): as BF16X3, the stride-1 forward launches on TWO fp16 planes (iaf_conv_bf3.hpp F16) from the pack L.wp2;
     // an operand beyond 65504 raises rng_err (mapped host memory): the next forward returns IAF_ERR_RANGE once and the conv runs bf16x3
     // from then on (f16_off) until iaf_conv3x3_set_precision(F16X2) re-arms
-    int precision = IAF_PRECISION_BF16X3;
-    unsigned* rng_err_host = nullptr;
-    unsigned* rng_err_dev = nullptr;
-    bool f16_off = false;
-    int packs = IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2;   // iaf_conv3x3_set_packs: which packs the prep launches keep up to date
+    RangeWord rng;
     int bf3_choice = 1;            // 1 size rule, 2 the shape in L.b_* (pinned by iaf_conv3x3_autotune), 3 fp32 kernel (measured faster)
     GemmLayer T;                   // transposed problem dX = W^T dY (valid when training)
     // deferred weight-norm backward (iaf_conv3x3_wn_bwd_batch_run): the reduced dW / db partials live here, not in the
@@ -38,15 +34,8 @@ struct iaf_conv3x3 {
 
 extern "C" int iaf_conv3x3_destroy(iaf_conv3x3_t* c) {
     if (!c) return IAF_ERR_NULL;
-    if (c->L.wp) (void)hipFree(c->L.wp);
-    if (c->L.wpt3) (void)hipFree(c->L.wpt3);
-    if (c->L.bias) (void)hipFree(c->L.bias);
-    if (c->L.wpt) (void)hipFree(c->L.wpt);
-    if (c->L.wp3) (void)hipFree(c->L.wp3);
-    if (c->L.wp2) (void)hipFree(c->L.wp2);
-    if (c->L.wpt2) (void)hipFree(c->L.wpt2);
-    if (c->rng_err_host) (void)hipHostFree(c->rng_err_host);
-    if (c->L.border) (void)hipFree(c->L.border);
+    gemm_layer_free(c->L);
+    c->rng.free();
     if (c->own_dW) (void)hipFree(c->own_dW);
     if (c->own_dbp) (void)hipFree(c->own_dbp);
     if (c->h_desc) (void)hipHostFree(c->h_desc);
@@ -58,16 +47,11 @@ extern "C" int iaf_conv3x3_destroy(iaf_conv3x3_t* c) {
 static inline bool conv_split(const iaf_conv3x3* c) { return c->precision != IAF_PRECISION_F32; }
 // the forward launches of this conv run the two-plane fp16 kernels now
 static inline bool conv_f16_active(const iaf_conv3x3* c) {
-    return c->precision == IAF_PRECISION_F16X2 && !c->f16_off && c->L.wp2 && !c->generic && !c->mask_mode;
+    return pack_f16_wanted(*c) && c->L.wp2 && !c->generic && !c->mask_mode;
 }
 // which packs a prep launch writes for a plain conv (iaf_conv3x3_set_packs; training keeps all of them)
 static inline void conv_prep_packs(const iaf_conv3x3* c, PrepLayer& P) {
-    const GemmLayer& L = c->L;
-    P.wp = (c->packs & IAF_PACK_F32) ? L.wp : nullptr;
-    P.wp3 = (c->packs & IAF_PACK_BF16X3) ? L.wp3 : nullptr;
-    P.wp2 = ((c->packs & IAF_PACK_F16X2) && conv_f16_active(c)) ? L.wp2 : nullptr;
-    P.rng_err = P.wp2 ? c->rng_err_dev : nullptr;
-    P.wpt = c->training ? L.wpt : nullptr;
+    prep_layer_packs(P, c->L, pack_prep_writes(*c, PACK_CONV, conv_f16_active(c), c->L.wp3 != nullptr, c->training), c->rng.dev);
 }
 static int conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out, int mask_mode);
 extern "C" int iaf_conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out) { return conv3x3_create(out, n_in, n_out, 0); }
@@ -103,17 +87,15 @@ static int conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out, int mask_mod
     default_tuning(L, false);
     L.live_macs_per_px = L.dense_macs_per_px = 9.0 * n_in * n_out;
     if (mask_mode) count_macs(L, n_in, n_out, L.zerodiag, 1);
-    const size_t wfloats = c->generic ? (size_t)MAXTAPS * n_in * n_out : (size_t)L.nchunk * MAXTAPS * L.ncot * 256;
     int rc;
-    if ((rc = (int)hipMalloc(&L.wp, wfloats * sizeof(float))) != 0 ||
+    if ((rc = (int)hipMalloc(&L.wp, c->generic ? (size_t)MAXTAPS * n_in * n_out * sizeof(float) : pack_bytes_f32(L, MAXTAPS))) != 0 ||
         (rc = (int)hipMalloc(&L.bias, ((size_t)L.ncot * 16 + (size_t)n_in) * sizeof(float))) != 0 ||   // + deconv norms
         (rc = (int)hipHostMalloc((void**)&c->h_desc, sizeof(PrepLayer))) != 0 ||
         (rc = (int)hipMalloc((void**)&c->d_desc, sizeof(PrepLayer))) != 0) {
         iaf_conv3x3_destroy(c);
         return rc;
     }
-    if (!c->generic && mask_mode == 0 && n_in % 32 == 0 &&
-        (rc = (int)hipMalloc(&L.wp3, (size_t)(n_in / 32) * MAXTAPS * L.ncot * 3 * 64 * 16)) != 0) {      // bf16x3 pack
+    if (!c->generic && mask_mode == 0 && n_in % 32 == 0 && (rc = (int)hipMalloc(&L.wp3, pack_bytes_split(L, MAXTAPS, 3))) != 0) {
         iaf_conv3x3_destroy(c);
         return rc;
     }
@@ -147,15 +129,15 @@ extern "C" int iaf_conv3x3_prepare(iaf_conv3x3_t* c, const float* V, const float
         memset(&a, 0, sizeof(a));
         a.nlayers = 1;
         PrepLayer& P = a.L[0];
-        P.V[0] = V; P.g[0] = g; P.b[0] = b; P.wp = L.wp; P.bias = L.bias; P.variant = c->variant; P.border = L.border;
-        P.cin = L.cin; P.cout_each = L.cout; P.ncot = L.ncot; P.nchunk = L.nchunk; P.zerodiag = L.zerodiag; P.npair = 1;
+        P.V[0] = V; P.g[0] = g; P.b[0] = b; P.wp = L.wp; P.variant = c->variant;
+        prep_layer_geometry(P, L, 0);
         hipLaunchKernelGGL(iaf_prep_kernel, dim3(L.ncot), dim3(256), 0, (hipStream_t)stream, a, 0u);
     } else {
         PrepLayer& P = *c->h_desc;
         memset(&P, 0, sizeof(P));
-        P.V[0] = V; P.g[0] = g; P.b[0] = b; P.bias = L.bias; P.variant = PREP_PLAIN9;
+        P.V[0] = V; P.g[0] = g; P.b[0] = b; P.variant = PREP_PLAIN9;
         conv_prep_packs(c, P);
-        P.cin = L.cin; P.cout_each = L.cout; P.ncot = L.ncot; P.nchunk = L.nchunk; P.npair = 1; P.tile_begin = 0;
+        prep_layer_geometry(P, L, 0);
         HIP_TRY(hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(PrepLayer), hipMemcpyHostToDevice, (hipStream_t)stream));
         hipLaunchKernelGGL(iaf_prep_plain_kernel, dim3(L.ncot), dim3(256), 0, (hipStream_t)stream, c->d_desc, (const int*)nullptr);
         if (c->training) {
@@ -176,7 +158,7 @@ extern "C" int iaf_conv3x3_prepare(iaf_conv3x3_t* c, const float* V, const float
 extern "C" int iaf_conv3x3_prepare_deconv(iaf_conv3x3_t* c, const float* V, const float* g, const float* b, void* stream) {
     if (!c || !V || !g || !b) return IAF_ERR_NULL;
     if (c->mask_mode) return IAF_ERR_UNSUPPORTED;
-    if (c->packs != (IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2)) return IAF_ERR_UNSUPPORTED;    // (the deconv packs derive from the fp32 one)
+    if (c->packs != IAF_PACK_ALL) return IAF_ERR_UNSUPPORTED;    // (the deconv packs derive from the fp32 one)
     GemmLayer& L = c->L;
     hipStream_t st = (hipStream_t)stream;
     float* inv_norm = L.bias + (size_t)L.ncot * 16;    // n_in floats behind the packed bias (conv3x3_create)
@@ -267,20 +249,24 @@ extern "C" int iaf_colsum(const float* mat, float* out, int m, int n, void* stre
 // weight prep of many plain convs in one launch (the four convs of every IAFLayer of a model): descriptors in device
 // memory, refreshed per run like iaf_prep_batch_run
 struct iaf_conv3x3_prep_batch {
-    int n, ntiles;
-    iaf_conv3x3** convs;
-    PrepLayer* h_layers;   // current descriptor table (host)
-    DescTable tab;         // its way to the device (see DescTable in iaf_engine.hip)
-    int* d_tile2layer;
+    std::vector<iaf_conv3x3*> convs;
+    BatchTable<PrepLayer> t;       // one descriptor per conv (BatchTable in iaf_engine.hip)
 };
 
 extern "C" int iaf_conv3x3_prep_batch_destroy(iaf_conv3x3_prep_batch_t* b) {
     if (!b) return IAF_ERR_NULL;
-    free(b->h_layers);
-    desc_destroy(&b->tab);
-    if (b->d_tile2layer) (void)hipFree(b->d_tile2layer);
-    free(b->convs);
+    b->t.destroy();
     delete b;
+    return IAF_OK;
+}
+
+// the convs a batch object takes (plain, on the MFMA path) and their tiles: one per 16 output channels
+static int conv_batch_tiles(iaf_conv3x3_t* const* convs, int n, std::vector<int>* tiles) {
+    for (int i = 0; i < n; ++i) {
+        if (!convs[i]) return IAF_ERR_NULL;
+        if (convs[i]->generic || convs[i]->mask_mode) return IAF_ERR_UNSUPPORTED;
+        tiles->push_back(convs[i]->L.ncot);
+    }
     return IAF_OK;
 }
 
@@ -288,39 +274,18 @@ extern "C" int iaf_conv3x3_prep_batch_create(iaf_conv3x3_prep_batch_t** out, iaf
     if (!out || !convs) return IAF_ERR_NULL;
     *out = nullptr;
     if (n <= 0) return IAF_ERR_SHAPE;
+    std::vector<int> tiles;
+    if (int rc = conv_batch_tiles(convs, n, &tiles)) return rc;
     iaf_conv3x3_prep_batch* b = new (std::nothrow) iaf_conv3x3_prep_batch();
     if (!b) return (int)hipErrorOutOfMemory;
-    memset(b, 0, sizeof(*b));
-    b->n = n;
-    b->convs = (iaf_conv3x3**)calloc(n, sizeof(iaf_conv3x3*));
-    int nt = 0;
+    b->convs.assign(convs, convs + n);
+    if (int rc = b->t.create(tiles, false)) { iaf_conv3x3_prep_batch_destroy(b); return rc; }
     for (int i = 0; i < n; ++i) {
-        if (!convs[i]) { iaf_conv3x3_prep_batch_destroy(b); return IAF_ERR_NULL; }
-        if (convs[i]->generic || convs[i]->mask_mode) { iaf_conv3x3_prep_batch_destroy(b); return IAF_ERR_UNSUPPORTED; }
-        b->convs[i] = convs[i];
-        nt += convs[i]->L.ncot;
-    }
-    b->ntiles = nt;
-    int* t2l = (int*)malloc(sizeof(int) * nt);
-    int rc;
-    b->h_layers = (PrepLayer*)calloc(n, sizeof(PrepLayer));
-    if (!b->h_layers) { free(t2l); iaf_conv3x3_prep_batch_destroy(b); return (int)hipErrorOutOfMemory; }
-    if ((rc = desc_init(&b->tab, sizeof(PrepLayer) * n)) != 0 ||
-        (rc = (int)hipMalloc((void**)&b->d_tile2layer, sizeof(int) * nt)) != 0) {
-        free(t2l); iaf_conv3x3_prep_batch_destroy(b); return rc;
-    }
-    int tile = 0;
-    for (int i = 0; i < n; ++i) {
-        const GemmLayer& L = convs[i]->L;
-        PrepLayer& P = b->h_layers[i];
-        P.bias = L.bias; P.variant = PREP_PLAIN9;
+        PrepLayer& P = b->t.h[i];
+        P.variant = PREP_PLAIN9;
         conv_prep_packs(convs[i], P);
-        P.cin = L.cin; P.cout_each = L.cout; P.ncot = L.ncot; P.nchunk = L.nchunk; P.npair = 1; P.tile_begin = tile;
-        for (int t = 0; t < L.ncot; ++t) t2l[tile++] = i;
+        prep_layer_geometry(P, convs[i]->L, b->t.begin[i]);
     }
-    rc = (int)hipMemcpy(b->d_tile2layer, t2l, sizeof(int) * nt, hipMemcpyHostToDevice);
-    free(t2l);
-    if (rc) { iaf_conv3x3_prep_batch_destroy(b); return rc; }
     *out = b;
     return IAF_OK;
 }
@@ -328,30 +293,26 @@ extern "C" int iaf_conv3x3_prep_batch_create(iaf_conv3x3_prep_batch_t** out, iaf
 extern "C" int iaf_conv3x3_prep_batch_run(iaf_conv3x3_prep_batch_t* b, const float* const* V, const float* const* g,
                                           const float* const* bias, void* stream) {
     if (!b || !V || !g || !bias) return IAF_ERR_NULL;
-    bool changed = false;
-    for (int i = 0; i < b->n; ++i) {
+    for (int i = 0; i < b->t.n; ++i) {
         if (!V[i] || !g[i] || !bias[i]) return IAF_ERR_NULL;
-        PrepLayer& P = b->h_layers[i];
-        PrepLayer N = P;                             // iaf_conv3x3_set_precision / _set_packs / _set_training / a range failure since the last run
-        conv_prep_packs(b->convs[i], N);
-        changed |= (P.V[0] != V[i]) | (P.g[0] != g[i]) | (P.b[0] != bias[i]) | (P.wpt != N.wpt) | (P.wp2 != N.wp2) | (P.rng_err != N.rng_err) |
-                   (P.wp != N.wp) | (P.wp3 != N.wp3);
-        P = N;
-        P.V[0] = V[i]; P.g[0] = g[i]; P.b[0] = bias[i];
+        b->t.set(i, [&](PrepLayer& P) {
+            P.V[0] = V[i]; P.g[0] = g[i]; P.b[0] = bias[i];
+            conv_prep_packs(b->convs[i], P);     // iaf_conv3x3_set_precision / _set_packs / _set_training / a range failure since the last run
+        });
     }
     hipStream_t st = (hipStream_t)stream;
-    const void* d_layers = nullptr;     // see iaf_prep_batch_run
-    { int rc = desc_upload(&b->tab, b->h_layers, changed, st, &d_layers); if (rc) return rc; }
-    hipLaunchKernelGGL(iaf_prep_plain_kernel, dim3(b->ntiles), dim3(256), 0, st, (const PrepLayer*)d_layers, b->d_tile2layer);
+    const PrepLayer* d_layers = nullptr;
+    if (int rc = b->t.upload(st, &d_layers)) return rc;
+    hipLaunchKernelGGL(iaf_prep_plain_kernel, dim3(b->t.ntiles), dim3(256), 0, st, d_layers, b->t.d_tile2layer);
     HIP_TRY(hipGetLastError());
     {
         PackT3Batch tb(st);
-        for (int i = 0; i < b->n; ++i)
-            if (b->convs[i]->training) { int rc = tb.add(b->convs[i]->L, MAXTAPS); if (rc) return rc; }
+        for (const iaf_conv3x3* c : b->convs)
+            if (c->training) { int rc = tb.add(c->L, MAXTAPS); if (rc) return rc; }
         int rc = tb.flush();
         if (rc) return rc;
     }
-    for (int i = 0; i < b->n; ++i) { b->convs[i]->prepared = true; b->convs[i]->deconv = false; }   // (packs of a conv2d now, as iaf_conv3x3_prepare leaves them)
+    for (iaf_conv3x3* c : b->convs) { c->prepared = true; c->deconv = false; }   // (packs of a conv2d now, as iaf_conv3x3_prepare leaves them)
     return IAF_OK;
 }
 
@@ -488,20 +449,6 @@ static int conv3x3_launch(GemmLayer& L, ConvP& p, int epi_sel, int inmode, bool 
     return (int)hipGetLastError();
 }
 
-// an F16 launch of this conv (or the prep of its pack) met an operand beyond fp16's range: said once (true: the caller returns IAF_ERR_RANGE);
-// bf16x3 from here on
-static bool conv_range_report(iaf_conv3x3* c) {
-    if (c->precision == IAF_PRECISION_F16X2 && !c->f16_off && c->rng_err_host && *(volatile unsigned*)c->rng_err_host) {
-        c->f16_off = true;
-        if (!(c->packs & IAF_PACK_BF16X3)) {           // (iaf_conv3x3_set_packs: the bf16x3 pack was not kept up to date -- every pack from the next prepare on)
-            c->packs = IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2;
-            c->prepared = false;
-        }
-        return true;
-    }
-    return false;
-}
-
 extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float* x2, int c_split, int elu_input,
                                    const float* residual, float* const* outs, const int* out_channels, int n_outs, int B,
                                    int H, int W, void* stream) {
@@ -544,8 +491,9 @@ extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float
         p.split_end[k] = ends[k < n_outs ? k : n_outs - 1];
         p.split_ptr[k] = outs[k < n_outs ? k : n_outs - 1];
     }
-    if (conv_range_report(c)) return IAF_ERR_RANGE;
-    if (!c->mask_mode && c->packs != (IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2)) {
+    // an F16 launch of this conv (or the prep of its pack) met an operand beyond fp16's range: said once; bf16x3 from here on
+    if (pack_range_report(*c, PACK_CONV, c->rng.peek())) return IAF_ERR_RANGE;
+    if (!c->mask_mode && c->packs != IAF_PACK_ALL) {
         // iaf_conv3x3_set_packs: the pack this launch reads must be one the prep launches write
         GemmLayer t = L;
         const bool split = conv_split(c) && !c->deconv && conv3x3_bf3_shape(t, c->bf3_choice, p.P, W, conv_f16_active(c));
@@ -554,7 +502,7 @@ extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float
         if (!(c->packs & need)) return IAF_ERR_NOT_PREPARED;
     }
     return conv3x3_launch(L, p, c->mask_mode ? EPI_PLAIN5 : EPI_PLAIN, IN_NCHW, c->mask_mode != 0, false, st, c->variant,
-                          (conv_split(c) && !c->deconv) ? c->bf3_choice : 3, conv_f16_active(c) ? c->rng_err_dev : nullptr);
+                          (conv_split(c) && !c->deconv) ? c->bf3_choice : 3, conv_f16_active(c) ? c->rng.dev : nullptr);
 }
 
 // ---- down_conv1 in prior form: the sample-mode top-down pass (tf_train.py:52-54, 56, 60-61; iaf_conv_bf3.hpp EPI_PRIOR) -------------
@@ -592,7 +540,8 @@ extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x
     GemmLayer& L = c->L;
     if (c->generic || c->mask_mode || c->deconv || !L.wp3 || !conv_split(c) || (n_z & 15) || (n_h & 15)) return IAF_ERR_UNSUPPORTED;
     if (!c->prepared) return IAF_ERR_NOT_PREPARED;
-    if (conv_range_report(c)) return IAF_ERR_RANGE;
+    // an F16 launch of this conv (or the prep of its pack) met an operand beyond fp16's range: said once; bf16x3 from here on
+    if (pack_range_report(*c, PACK_CONV, c->rng.peek())) return IAF_ERR_RANGE;
     const bool f16 = iaf_conv3x3_runs_f16x2(c, B, H, W) != 0;
     if (!(c->packs & (f16 ? IAF_PACK_F16X2 : IAF_PACK_BF16X3))) return IAF_ERR_NOT_PREPARED;    // (iaf_conv3x3_set_packs)
     ConvP p;
@@ -606,7 +555,7 @@ extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x
     p.x = x; p.in_elu = elu_input ? 1 : 0;
     p.eps = eps; p.out0 = z; p.out1 = h_det;
     p.wp = f16 ? (const float*)L.wp2 : (const float*)L.wp3; p.bias = L.bias;
-    p.rng_err = f16 ? c->rng_err_dev : nullptr;
+    p.rng_err = f16 ? c->rng.dev : nullptr;
     for (int t = 0; t < MAXTAPS; ++t) { p.tap_dh[t] = t / 3 - 1; p.tap_dw[t] = t % 3 - 1; }     // cross-correlation, SAME
     const int tm = 32;                                                                             // ppw 2, pxt 1
     p.halo_before = W + 1;
@@ -751,52 +700,29 @@ extern "C" int iaf_conv3x3_forward_deconv(iaf_conv3x3_t* c, const float* x, cons
 // which packs the prep launches of a plain conv keep up to date (as iaf_stack_set_packs): a conv that runs at ONE size needs one
 extern "C" int iaf_conv3x3_set_packs(iaf_conv3x3_t* c, int packs) {
     if (!c) return IAF_ERR_NULL;
-    if (packs & ~(IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2)) return IAF_ERR_SHAPE;
-    if (!packs) return IAF_ERR_SHAPE;
-    const int all = IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2;
-    if (packs != all && (c->generic || c->mask_mode || c->training || c->deconv)) return IAF_ERR_UNSUPPORTED;
-    if ((packs & IAF_PACK_BF16X3) && !(packs & IAF_PACK_F32) && !c->L.wp3) return IAF_ERR_UNSUPPORTED;      // (no split pack for this conv)
-    if ((packs & IAF_PACK_F16X2) && !(packs & (IAF_PACK_F32 | IAF_PACK_BF16X3)) && !conv_f16_active(c)) return IAF_ERR_UNSUPPORTED;
-    if (packs & ~c->packs) c->prepared = false;              // a pack that was not kept up to date comes back: the next prepare fills it
-    c->packs = packs;
-    return IAF_OK;
+    PackFacts f;
+    f.generic = c->generic; f.masked = c->mask_mode != 0; f.training = c->training; f.deconv = c->deconv;
+    f.all_split = c->L.wp3 != nullptr; f.f16_active = conv_f16_active(c);
+    return pack_conv_set_packs(*c, packs, f);
 }
 extern "C" int iaf_conv3x3_set_precision(iaf_conv3x3_t* c, int precision) {
     if (!c) return IAF_ERR_NULL;
     if (precision != IAF_PRECISION_F32 && precision != IAF_PRECISION_BF16X3 && precision != IAF_PRECISION_F16X2) return IAF_ERR_SHAPE;
+    bool new_pack = false;
     if (precision == IAF_PRECISION_F16X2) {
         GemmLayer& L = c->L;
         if (c->generic || c->mask_mode || !L.wp3) return IAF_ERR_UNSUPPORTED;       // (plain convs with c_in % 32 == 0: the same fragments, two planes)
-        if (!c->rng_err_host) {
-            if (hipHostMalloc((void**)&c->rng_err_host, 64, hipHostMallocMapped) != hipSuccess) { c->rng_err_host = nullptr; return (int)hipErrorOutOfMemory; }
-            *(volatile unsigned*)c->rng_err_host = 0u;
-            if (hipHostGetDevicePointer((void**)&c->rng_err_dev, c->rng_err_host, 0) != hipSuccess) {
-                (void)hipHostFree(c->rng_err_host); c->rng_err_host = nullptr; c->rng_err_dev = nullptr;
-                return (int)hipErrorOutOfMemory;
-            }
-        }
+        if (int rc = c->rng.alloc()) return rc;
         if (!L.wp2) {
-            HIP_TRY(hipMalloc(&L.wp2, (size_t)(L.cin / 32) * MAXTAPS * L.ncot * 2 * 1024));
-            c->prepared = false;                             // the next prepare fills it
+            HIP_TRY(hipMalloc(&L.wp2, pack_bytes_split(L, MAXTAPS, 2)));
+            new_pack = true;
         }
-        if (c->f16_off || *(volatile unsigned*)c->rng_err_host) {        // re-armed after a range failure
-            HIP_TRY(hipDeviceSynchronize());
-            *(volatile unsigned*)c->rng_err_host = 0u;
-            c->f16_off = false;
-            c->prepared = false;
-        }
-        if (c->precision != IAF_PRECISION_F16X2) c->prepared = false;     // the fp16 pack has not been kept up to date
     }
-    c->precision = precision;
-    return IAF_OK;
+    return pack_set_precision(*c, PACK_CONV, precision, new_pack, c->rng.peek()) ? c->rng.rearm() : IAF_OK;
 }
 extern "C" int iaf_conv3x3_range_errors(const iaf_conv3x3_t* c, unsigned* errors) {
     if (!c || !errors) return IAF_ERR_NULL;
-    *errors = 0;
-    if (!c->rng_err_host) return IAF_OK;
-    HIP_TRY(hipDeviceSynchronize());
-    *errors = *(volatile unsigned*)c->rng_err_host;
-    return IAF_OK;
+    return c->rng.read(errors);
 }
 // 1 if a forward call at this size would run the bf16x3 kernel
 extern "C" int iaf_conv3x3_runs_bf16x3(iaf_conv3x3_t* c, int B, int H, int W) {
@@ -939,20 +865,12 @@ extern "C" int iaf_conv3x3_set_training(iaf_conv3x3_t* c, int on) {
         return IAF_OK;
     }
     GemmLayer& L = c->L;
-    if (!L.wpt) HIP_TRY(hipMalloc(&L.wpt, (size_t)L.nchunk * MAXTAPS * L.ncot * 256 * sizeof(float)));
-    // the transposed pack as bf16x3 (iaf_pack_t3_kernel): the data gradient on the bf16 matrix cores (even K tile counts)
-    if (!L.wpt3 && L.ncot % 2 == 0) HIP_TRY(hipMalloc(&L.wpt3, (size_t)(L.ncot / 2) * MAXTAPS * L.nchunk * 3 * 64 * 16));
-    // ... and as two fp16 planes: the data gradient of a conv whose arithmetic is IAF_PRECISION_F16X2 (iaf_conv_bf3.hpp DG16; IAF_DGRAD_F16=0: dev knob)
+    // the transposed pack, also as bf16x3 (iaf_pack_t3_kernel: the data gradient on the bf16 matrix cores, even K tile counts) and as two
+    // fp16 planes: the data gradient of a conv whose arithmetic is IAF_PRECISION_F16X2 (iaf_conv_bf3.hpp DG16; IAF_DGRAD_F16=0: dev knob)
     static const bool dg16_env = !(getenv("IAF_DGRAD_F16") && getenv("IAF_DGRAD_F16")[0] == '0');
-    if (dg16_env && L.wpt3 && !L.wpt2) HIP_TRY(hipMalloc(&L.wpt2, (size_t)(L.ncot / 2) * MAXTAPS * L.nchunk * 2 * 64 * 16));
-    GemmLayer& T = c->T;
-    T = GemmLayer();
-    T.cin = L.cout; T.cout = L.cin; T.nchunk = L.ncot; T.ncot = L.nchunk; T.zerodiag = 0; T.npair = 1; T.full3x3 = true;
-    T.wp = L.wpt; T.wp3 = L.wpt3; T.wp2 = L.wpt2; T.nt = 1; T.pxt = 4; T.wco = 1; T.ks = 1; T.user_tuned = false;
-    T.dbg = L.dbg; T.dbg_bytes = L.dbg_bytes;
+    if (int rc = gemm_layer_set_training(L, c->T, MAXTAPS, dg16_env)) return rc;
     c->training = true;
-    c->packs = IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2;     // (training keeps every pack)
-    c->prepared = false;      // the transposed pack is written by the next prepare
+    pack_set_training(*c);    // (training keeps every pack)
     return IAF_OK;
 }
 
@@ -1076,7 +994,7 @@ extern "C" int iaf_conv3x3_backward(iaf_conv3x3_t* c, const float* x, const floa
         }
         // bf16x3 unless the conv's precision is fp32 or a backward search measured the fp32 kernel faster at this size
         const int choice3 = (!conv_split(c) || c->bf3_choice == 3 || !c->T.wp3) ? 3 : (c->T.tuned_P == (long long)P && c->T.tuned_W == W && !c->T.tuned_bf3) ? 3 : 1;
-        const bool dgrad16 = c->precision == IAF_PRECISION_F16X2 && !c->f16_off && c->T.wp2 != nullptr && !c->deconv;
+        const bool dgrad16 = pack_f16_wanted(*c) && c->T.wp2 != nullptr && !c->deconv;
         if ((rc = conv3x3_launch(c->T, p, EPI_DGRAD9, IN_PIXMAJOR, false, true, st, IAF_VARIANT_TF, choice3, nullptr, dgrad16))) return rc;
     }
     // (3) weight gradient: partials over pixel ranges, then reduce (+ column sums of dY for db)
@@ -1212,21 +1130,13 @@ extern "C" int iaf_conv3x3_set_defer_weightnorm(iaf_conv3x3_t* c, int on) {
 }
 
 struct iaf_conv3x3_wn_bwd_batch {
-    int n, ntiles;
-    iaf_conv3x3** convs;
-    WnBwdLayer* h_layers;   // current descriptor table (host)
-    DescTable tab;          // its way to the device (see DescTable in iaf_engine.hip)
-    int* d_tile2layer;
-    int* d_tile_begin;
+    std::vector<iaf_conv3x3*> convs;
+    BatchTable<WnBwdLayer> t;      // one descriptor per conv
 };
 
 extern "C" int iaf_conv3x3_wn_bwd_batch_destroy(iaf_conv3x3_wn_bwd_batch_t* b) {
     if (!b) return IAF_ERR_NULL;
-    free(b->h_layers);
-    desc_destroy(&b->tab);
-    if (b->d_tile2layer) (void)hipFree(b->d_tile2layer);
-    if (b->d_tile_begin) (void)hipFree(b->d_tile_begin);
-    free(b->convs);
+    b->t.destroy();
     delete b;
     return IAF_OK;
 }
@@ -1235,42 +1145,17 @@ extern "C" int iaf_conv3x3_wn_bwd_batch_create(iaf_conv3x3_wn_bwd_batch_t** out,
     if (!out || !convs) return IAF_ERR_NULL;
     *out = nullptr;
     if (n <= 0) return IAF_ERR_SHAPE;
+    std::vector<int> tiles;
+    if (int rc = conv_batch_tiles(convs, n, &tiles)) return rc;
     iaf_conv3x3_wn_bwd_batch* b = new (std::nothrow) iaf_conv3x3_wn_bwd_batch();
     if (!b) return (int)hipErrorOutOfMemory;
-    memset(b, 0, sizeof(*b));
-    b->n = n;
-    b->convs = (iaf_conv3x3**)calloc(n, sizeof(iaf_conv3x3*));
-    int nt = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!convs[i]) { iaf_conv3x3_wn_bwd_batch_destroy(b); return IAF_ERR_NULL; }
-        if (convs[i]->generic || convs[i]->mask_mode) { iaf_conv3x3_wn_bwd_batch_destroy(b); return IAF_ERR_UNSUPPORTED; }
-        b->convs[i] = convs[i];
-        nt += convs[i]->L.ncot;
-    }
-    b->ntiles = nt;
-    int* t2l = (int*)malloc(sizeof(int) * nt);
-    int* tb = (int*)malloc(sizeof(int) * (n + 1));
-    int rc;
-    b->h_layers = (WnBwdLayer*)calloc(n, sizeof(WnBwdLayer));
-    if (!b->h_layers) { free(t2l); free(tb); iaf_conv3x3_wn_bwd_batch_destroy(b); return (int)hipErrorOutOfMemory; }
-    if ((rc = desc_init(&b->tab, sizeof(WnBwdLayer) * n)) != 0 ||
-        (rc = (int)hipMalloc((void**)&b->d_tile2layer, sizeof(int) * nt)) != 0 ||
-        (rc = (int)hipMalloc((void**)&b->d_tile_begin, sizeof(int) * (n + 1))) != 0) {
-        free(t2l); free(tb); iaf_conv3x3_wn_bwd_batch_destroy(b); return rc;
-    }
-    int tile = 0;
+    b->convs.assign(convs, convs + n);
+    if (int rc = b->t.create(tiles, true)) { iaf_conv3x3_wn_bwd_batch_destroy(b); return rc; }
     for (int i = 0; i < n; ++i) {
         const GemmLayer& L = convs[i]->L;
-        WnBwdLayer& w = b->h_layers[i];
+        WnBwdLayer& w = b->t.h[i];
         w.cin = L.cin; w.cout = L.cout; w.cout_packed = L.cout; w.pack_stride = 1;
-        tb[i] = tile;
-        for (int t = 0; t < L.ncot; ++t) t2l[tile++] = i;
     }
-    tb[n] = tile;
-    rc = (int)hipMemcpy(b->d_tile2layer, t2l, sizeof(int) * nt, hipMemcpyHostToDevice);
-    if (!rc) rc = (int)hipMemcpy(b->d_tile_begin, tb, sizeof(int) * (n + 1), hipMemcpyHostToDevice);
-    free(t2l); free(tb);
-    if (rc) { iaf_conv3x3_wn_bwd_batch_destroy(b); return rc; }
     *out = b;
     return IAF_OK;
 }
@@ -1278,23 +1163,19 @@ extern "C" int iaf_conv3x3_wn_bwd_batch_create(iaf_conv3x3_wn_bwd_batch_t** out,
 extern "C" int iaf_conv3x3_wn_bwd_batch_run(iaf_conv3x3_wn_bwd_batch_t* b, const float* const* V, const float* const* g,
                                             float* const* dV, float* const* dg, float* const* db, void* stream) {
     if (!b || !V || !g || !dV || !dg || !db) return IAF_ERR_NULL;
-    bool changed = false;
-    for (int i = 0; i < b->n; ++i) {
-        iaf_conv3x3* c = b->convs[i];
+    for (int i = 0; i < b->t.n; ++i) {
+        const iaf_conv3x3* c = b->convs[i];
         if (!c->defer_wn || (!c->pending && !c->deconv)) return IAF_ERR_NOT_PREPARED;
         if (!V[i] || !g[i] || !dV[i] || !dg[i] || !db[i]) return IAF_ERR_NULL;
-        WnBwdLayer& w = b->h_layers[i];
-        changed |= (w.skip != (c->deconv ? 1 : 0));
-        w.skip = c->deconv ? 1 : 0;        // a deconv2d pushes its gradient through its own norm inside iaf_conv3x3_backward
-        changed |= (w.V != V[i]) | (w.g != g[i]) | (w.dV != dV[i]) | (w.dg != dg[i]) | (w.db != db[i]) |
-                   (w.dW != c->own_dW) | (w.dbp != c->own_dbp) | (w.nslab != c->pend_nslab);
-        w.V = V[i]; w.g = g[i]; w.dV = dV[i]; w.dg = dg[i]; w.db = db[i];
-        w.dW = c->own_dW; w.dbp = c->own_dbp; w.nslab = c->pend_nslab;
+        b->t.set(i, [&](WnBwdLayer& w) {
+            w.skip = c->deconv ? 1 : 0;        // a deconv2d pushes its gradient through its own norm inside iaf_conv3x3_backward
+            w.V = V[i]; w.g = g[i]; w.dV = dV[i]; w.dg = dg[i]; w.db = db[i];
+            w.dW = c->own_dW; w.dbp = c->own_dbp; w.nslab = c->pend_nslab;
+        });
     }
     hipStream_t st = (hipStream_t)stream;
-    const void* d_layers = nullptr;
-    { int rc = desc_upload(&b->tab, b->h_layers, changed, st, &d_layers); if (rc) return rc; }
-    hipLaunchKernelGGL(iaf_wn_bwd_plain_batch_kernel, dim3(b->ntiles), dim3(256), 0, st, (const WnBwdLayer*)d_layers, b->d_tile2layer,
-                       b->d_tile_begin);
+    const WnBwdLayer* d_layers = nullptr;
+    if (int rc = b->t.upload(st, &d_layers)) return rc;
+    hipLaunchKernelGGL(iaf_wn_bwd_plain_batch_kernel, dim3(b->t.ntiles), dim3(256), 0, st, d_layers, b->t.d_tile2layer, b->t.d_tile_begin);
     return (int)hipGetLastError();
 }

@@ -47,6 +47,7 @@
 #include <mutex>
 #include <new>
 #include <unordered_set>
+#include <vector>
 
 #include "iaf_hip.h"
 
@@ -64,6 +65,8 @@
 #include "iaf_kernels_generic.hpp"
 #include "iaf_kernels_resample.hpp"
 #include "iaf_kernels_rng.hpp"
+
+#include "iaf_pack_state.hpp"   // the pack / precision / range protocol of iaf_stack and iaf_conv3x3 (no HIP in it: walked on a CPU by tests/test_pack_state.py)
 
 // ---------------------------------------------------------------------------------------------
 // host side: stack object
@@ -98,7 +101,39 @@ struct GemmLayer {
     double live_macs_per_px, dense_macs_per_px;
 };
 
-struct iaf_stack {
+// the HIP half of the range word (iaf_pack_state.hpp has the protocol): mapped pinned memory an fp16 launch raises, read by the host
+// without synchronising
+struct RangeWord {
+    unsigned* host = nullptr;
+    unsigned* dev = nullptr;       // its device-side alias
+    int alloc() {
+        if (host) return IAF_OK;
+        if (hipHostMalloc((void**)&host, 64, hipHostMallocMapped) != hipSuccess) { host = nullptr; return (int)hipErrorOutOfMemory; }
+        *(volatile unsigned*)host = 0u;
+        if (hipHostGetDevicePointer((void**)&dev, host, 0) != hipSuccess) { free(); return (int)hipErrorOutOfMemory; }
+        return IAF_OK;
+    }
+    unsigned peek() const { return host ? *(volatile unsigned*)host : 0u; }
+    // every launch so far has had its say
+    int read(unsigned* errors) const {
+        *errors = 0;
+        if (!host) return IAF_OK;
+        if (hipError_t e = hipDeviceSynchronize()) return (int)e;
+        *errors = peek();
+        return IAF_OK;
+    }
+    int rearm() {
+        if (hipError_t e = hipDeviceSynchronize()) return (int)e;
+        *(volatile unsigned*)host = 0u;
+        return IAF_OK;
+    }
+    void free() {
+        if (host) (void)hipHostFree(host);
+        host = dev = nullptr;
+    }
+};
+
+struct iaf_stack : PackState {     // precision (forward convs: F32 = the exact fp32 MFMA, else split products), packs, f16_off, prepared
     int n_z, n_h, depth_ar, variant;
     int nlayers;          // depth_ar + 1
     GemmLayer L[MAX_GEMM_LAYERS];
@@ -129,22 +164,16 @@ struct iaf_stack {
     bool xch_on = true;                   // iaf_stack_set_halo_exchange
     unsigned xch_knob = 0;                // iaf_stack_set_halo_exchange_debug
     int fb_groups = 1;                    // iaf_stack_set_free_bits_groups: the posterior block's free-bits mean per contiguous run of B / fb_groups rows
-    int precision = IAF_PRECISION_BF16X3;   // forward convs: bf16x3 split products on the bf16 MFMA, or the exact fp32 MFMA
     int fuse_first = 2;       // first masked conv fused into the second one's kernel: 0 never, 1 whenever possible, 2 only where
                               // iaf_stack_autotune measured it faster (on MI355X at the BASELINE sizes it is not: docs/LAB_NOTEBOOK_r01-r03.md 4.8)
     int fuse_step = 1;        // the whole step as ONE launch (iaf_step_fused.hpp): 0 never, 1 where a compiled geometry covers it and
                               // the size rule / autotune's measurement favours it, 2 wherever a compiled geometry covers it
     long long fs_P = -1; int fs_W = 0; bool fs_on = false;   // ... unless iaf_stack_autotune measured this size: then what it found
     int fs_force = -1;        // (autotune's own measurements: -1 off, 0 / 1 = take this path regardless)
-    bool skip_f32_pack = false;   // iaf_stack_set_packs: the prep launches write the bf16x3 packs only
-    bool skip_bf3_pack = false;   // ... the two-plane fp16 packs only (IAF_PRECISION_F16X2 stacks whose every launch is an F16 step kernel)
     // IAF_PRECISION_F16X2: the word the F16 kernels (and the prep of their packs) raise when an operand lies beyond fp16's largest finite
     // number -- mapped pinned memory, read without synchronising at the stack's next launch, which then returns IAF_ERR_RANGE once and
     // the stack goes on with the bf16x3 kernels (f16_off) until iaf_stack_set_precision(F16X2) is called again
-    unsigned* rng_err_host = nullptr;
-    unsigned* rng_err_dev = nullptr;
-    bool f16_off = false;
-    bool prepared;
+    RangeWord rng;
     size_t weight_bytes;  // raw V/g/b bytes of the stack (for the algorithmic byte count)
     // optional per-launch event timing of one layer
     unsigned long long* dbg = nullptr; int dbg_layer = -1;
@@ -258,6 +287,90 @@ static int desc_upload(DescTable* t, const void* host, bool changed, hipStream_t
     }
     *d_out = t->d_tabs;
     return IAF_OK;
+}
+
+// ---- the tables of a batched launch (iaf_prep_batch, iaf_wn_bwd_batch and their iaf_conv3x3_* twins): one descriptor of type D per
+// object, the launch's tile -> descriptor map and, for the weight-norm batches, every descriptor's first tile on the device too.
+template <class D> struct BatchTable {
+    int n = 0, ntiles = 0;
+    D* h = nullptr;                // the current descriptors (host; a run changes them through set())
+    std::vector<int> begin;        // [n + 1]: first tile of descriptor i
+    bool dirty = false;            // h differs from what upload() last carried
+    DescTable tab{};               // its way to the device
+    int* d_tile2layer = nullptr;
+    int* d_tile_begin = nullptr;   // begin[] on the device (with_begin)
+    // tiles[i]: workgroups of descriptor i.  On an error the owner's destroy() frees what was made.
+    int create(const std::vector<int>& tiles, bool with_begin) {
+        n = (int)tiles.size();
+        begin.assign(n + 1, 0);
+        std::vector<int> t2l;
+        for (int i = 0; i < n; ++i) { begin[i + 1] = begin[i] + tiles[i]; t2l.insert(t2l.end(), tiles[i], i); }
+        ntiles = begin[n];
+        if (!(h = (D*)calloc(n, sizeof(D)))) return (int)hipErrorOutOfMemory;
+        if (int rc = desc_init(&tab, sizeof(D) * n)) return rc;
+        HIP_TRY(hipMalloc((void**)&d_tile2layer, sizeof(int) * ntiles));
+        HIP_TRY(hipMemcpy(d_tile2layer, t2l.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
+        if (!with_begin) return IAF_OK;
+        HIP_TRY(hipMalloc((void**)&d_tile_begin, sizeof(int) * (n + 1)));
+        return (int)hipMemcpy(d_tile_begin, begin.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice);
+    }
+    void destroy() {
+        free(h);
+        desc_destroy(&tab);
+        if (d_tile2layer) (void)hipFree(d_tile2layer);
+        if (d_tile_begin) (void)hipFree(d_tile_begin);
+    }
+    // this run's descriptor i: build the new one from the old (fill sets what a run decides), compare, assign
+    template <class F> void set(int i, F fill) {
+        D nw;
+        memcpy(&nw, &h[i], sizeof(D));
+        fill(nw);
+        if (!memcmp(&nw, &h[i], sizeof(D))) return;
+        memcpy(&h[i], &nw, sizeof(D));
+        dirty = true;
+    }
+    // the table only travels when a descriptor changed (a training loop passes the same buffers every step)
+    int upload(hipStream_t st, const D** d_out) {
+        const void* d = nullptr;
+        if (int rc = desc_upload(&tab, h, dirty, st, &d)) return rc;
+        dirty = false;
+        *d_out = (const D*)d;
+        return IAF_OK;
+    }
+};
+
+// ---- what a GemmLayer owns ----------------------------------------------------------------------------------------------------------
+// bytes of its packs (taps: NTAPS masked, MAXTAPS plain): the fp32 fragments (forward and transposed: the same count); `planes` bf16 (3) or
+// fp16 (2) planes of the forward problem (c_in % 32 == 0) and of the transposed one (even co tile counts)
+static size_t pack_bytes_f32(const GemmLayer& L, int taps) { return (size_t)L.nchunk * taps * L.ncot * 256 * sizeof(float); }
+static size_t pack_bytes_split(const GemmLayer& L, int taps, int planes) { return (size_t)(L.cin / 32) * taps * L.ncot * planes * 1024; }
+static size_t pack_bytes_split_t(const GemmLayer& L, int taps, int planes) { return (size_t)(L.ncot / 2) * taps * L.nchunk * planes * 1024; }
+static void gemm_layer_free(GemmLayer& L) {
+    void* const own[] = {L.wp, L.bias, L.border, L.wpt, L.wpt3, L.wp3, L.wp2, L.wpt2, L.lim};
+    for (void* q : own)
+        if (q) (void)hipFree(q);
+}
+// training: the transposed packs of forward layer L (the next prepare writes them; f16: also as two fp16 planes, iaf_conv_bf3.hpp DG16)
+// and T, the transposed problem dX = W^T dY, which runs the bf16x3 kernel where its launch-shape rule takes it
+static int gemm_layer_set_training(GemmLayer& L, GemmLayer& T, int taps, bool f16) {
+    if (!L.wpt) HIP_TRY(hipMalloc(&L.wpt, pack_bytes_f32(L, taps)));
+    if (!L.wpt3 && L.ncot % 2 == 0) HIP_TRY(hipMalloc(&L.wpt3, pack_bytes_split_t(L, taps, 3)));
+    if (f16 && L.wpt3 && !L.wpt2) HIP_TRY(hipMalloc(&L.wpt2, pack_bytes_split_t(L, taps, 2)));
+    T = GemmLayer();
+    T.cin = L.cout; T.cout = L.cin; T.nchunk = L.ncot; T.ncot = L.nchunk; T.zerodiag = L.zerodiag; T.npair = 1; T.full3x3 = L.full3x3;
+    T.wp = L.wpt; T.wp3 = L.wpt3; T.wp2 = L.wpt2; T.nt = 1; T.pxt = 4; T.wco = 1; T.ks = 1;
+    T.dbg = L.dbg; T.dbg_bytes = L.dbg_bytes;
+    return IAF_OK;
+}
+// a prep descriptor's geometry, and the packs the launch writes (which: pack_prep_writes, iaf_pack_state.hpp)
+static void prep_layer_geometry(PrepLayer& P, const GemmLayer& L, int tile_begin) {
+    P.bias = L.bias; P.border = L.border;
+    P.cin = L.cin; P.cout_each = L.cout / L.npair; P.ncot = L.ncot; P.nchunk = L.nchunk;
+    P.zerodiag = L.zerodiag; P.npair = L.npair; P.tile_begin = tile_begin;
+}
+static void prep_layer_packs(PrepLayer& P, const GemmLayer& L, PackWrites w, unsigned* rng) {
+    P.wp = w.wp ? L.wp : nullptr; P.wp3 = w.wp3 ? L.wp3 : nullptr; P.wpt = w.wpt ? L.wpt : nullptr;
+    P.wp2 = w.wp2 ? L.wp2 : nullptr; P.rng_err = w.wp2 ? rng : nullptr;
 }
 
 // The compiled launch shapes (iaf_variants.def), one translation unit each: a table per family of {shape, picker}, in search order.
@@ -423,13 +536,11 @@ extern "C" int iaf_stack_create(iaf_stack_t** out, int n_z, int n_h, int depth_a
         count_macs(L, cin, each, L.zerodiag, L.npair);
         s->weight_bytes += (size_t)L.npair * (9 * (size_t)(cin + (variant != IAF_VARIANT_TF ? 1 : 0)) * each + 2 * (size_t)each) * sizeof(float);
         int rc;
-        const size_t wfloats = generic ? (size_t)NTAPS * cin * L.cout : (size_t)L.nchunk * NTAPS * L.ncot * 256;
-        if ((rc = (int)hipMalloc(&L.wp, wfloats * sizeof(float))) != 0 ||
+        if ((rc = (int)hipMalloc(&L.wp, generic ? (size_t)NTAPS * cin * L.cout * sizeof(float) : pack_bytes_f32(L, NTAPS))) != 0 ||
             (rc = (int)hipMalloc(&L.bias, (size_t)L.cout * sizeof(float))) != 0 ||
             (variant != IAF_VARIANT_TF && (rc = (int)hipMalloc(&L.border, (size_t)4 * L.cout * sizeof(float))) != 0) ||
             (rc = (int)hipMalloc(&L.lim, (size_t)L.ncot * sizeof(int))) != 0 ||
-            (!generic && cin % 32 == 0 &&
-             (rc = (int)hipMalloc(&L.wp3, (size_t)(cin / 32) * NTAPS * L.ncot * 3 * 1024)) != 0)) {
+            (!generic && cin % 32 == 0 && (rc = (int)hipMalloc(&L.wp3, pack_bytes_split(L, NTAPS, 3))) != 0)) {
             iaf_stack_destroy(s);
             return rc;
         }
@@ -523,19 +634,10 @@ static void xch_free_sets(iaf_stack_t* s) {
 extern "C" int iaf_stack_destroy(iaf_stack_t* s) {
     if (!s) return IAF_ERR_NULL;
     prof_free(s);
-    for (int l = 0; l < s->nlayers; ++l) {
-        if (s->L[l].wp) (void)hipFree(s->L[l].wp);
-        if (s->L[l].bias) (void)hipFree(s->L[l].bias);
-        if (s->L[l].border) (void)hipFree(s->L[l].border);
-        if (s->L[l].wpt) (void)hipFree(s->L[l].wpt);
-        if (s->L[l].wpt3) (void)hipFree(s->L[l].wpt3);
-        if (s->L[l].wp3) (void)hipFree(s->L[l].wp3);
-        if (s->L[l].wp2) (void)hipFree(s->L[l].wp2);
-        if (s->L[l].lim) (void)hipFree(s->L[l].lim);
-    }
+    for (int l = 0; l < s->nlayers; ++l) gemm_layer_free(s->L[l]);
     xch_free_sets(s);
     if (s->xch_err_host) (void)hipHostFree(s->xch_err_host);
-    if (s->rng_err_host) (void)hipHostFree(s->rng_err_host);
+    s->rng.free();
     delete s;
     return IAF_OK;
 }
@@ -610,7 +712,7 @@ static bool bf3_select(const iaf_stack_t* s, GemmLayer& L, int epi, bool negate_
 static inline bool prec_split(const iaf_stack_t* s) { return s->precision != IAF_PRECISION_F32; }
 // the F16 step kernels are in use: the precision asks for them, every layer has the pack, no range failure has been seen
 static inline bool f16_active(const iaf_stack_t* s) {
-    if (s->precision != IAF_PRECISION_F16X2 || s->f16_off || s->generic) return false;
+    if (!pack_f16_wanted(*s) || s->generic) return false;
     for (int l = 0; l < s->nlayers; ++l) if (!s->L[l].wp2) return false;
     return true;
 }
@@ -618,55 +720,30 @@ static inline bool f16_active(const iaf_stack_t* s) {
 extern "C" int iaf_stack_set_precision(iaf_stack_t* s, int precision) {
     if (!s) return IAF_ERR_NULL;
     if (precision != IAF_PRECISION_F32 && precision != IAF_PRECISION_BF16X3 && precision != IAF_PRECISION_F16X2) return IAF_ERR_SHAPE;
+    bool new_pack = false;
     if (precision == IAF_PRECISION_F16X2) {
         if (s->generic) return IAF_ERR_UNSUPPORTED;
         for (int l = 0; l < s->nlayers; ++l) if (!s->L[l].wp3) return IAF_ERR_UNSUPPORTED;      // (c_in % 32: the same fragments, two planes)
-        if (!s->rng_err_host) {
-            if (hipHostMalloc((void**)&s->rng_err_host, 64, hipHostMallocMapped) != hipSuccess) { s->rng_err_host = nullptr; return (int)hipErrorOutOfMemory; }
-            *(volatile unsigned*)s->rng_err_host = 0u;
-            if (hipHostGetDevicePointer((void**)&s->rng_err_dev, s->rng_err_host, 0) != hipSuccess) {
-                (void)hipHostFree(s->rng_err_host); s->rng_err_host = nullptr; s->rng_err_dev = nullptr;
-                return (int)hipErrorOutOfMemory;
-            }
-        }
+        if (int rc = s->rng.alloc()) return rc;
         for (int l = 0; l < s->nlayers; ++l) {
             GemmLayer& L = s->L[l];
             if (L.wp2) continue;
-            HIP_TRY(hipMalloc(&L.wp2, (size_t)(L.cin / 32) * NTAPS * L.ncot * 2 * 1024));
-            s->prepared = false;                             // the next prepare fills it
+            HIP_TRY(hipMalloc(&L.wp2, pack_bytes_split(L, NTAPS, 2)));
+            new_pack = true;
         }
-        if (s->f16_off || *(volatile unsigned*)s->rng_err_host) {       // re-armed after a range failure
-            HIP_TRY(hipDeviceSynchronize());
-            *(volatile unsigned*)s->rng_err_host = 0u;
-            s->f16_off = false;
-            s->prepared = false;
-        }
-    } else if (s->skip_bf3_pack) {
-        s->skip_bf3_pack = false;                            // (the bf16x3 pack is wanted again)
-        s->prepared = false;
     }
-    if (precision == IAF_PRECISION_F16X2 && s->precision != IAF_PRECISION_F16X2) s->prepared = false;   // the fp16 pack has not been kept up to date
-                                                             // (away from F16X2: the packs the other kernels read were written all along)
-    s->precision = precision;
-    return IAF_OK;
+    // (away from F16X2: the packs the other kernels read were written all along -- unless iaf_stack_set_packs dropped the bf16x3 one)
+    return pack_set_precision(*s, PACK_STACK, precision, new_pack, s->rng.peek()) ? s->rng.rearm() : IAF_OK;
 }
 
 extern "C" int iaf_stack_range_errors(const iaf_stack_t* s, unsigned* errors) {
     if (!s || !errors) return IAF_ERR_NULL;
-    *errors = 0;
-    if (!s->rng_err_host) return IAF_OK;
-    HIP_TRY(hipDeviceSynchronize());                         // (every launch so far has had its say)
-    *errors = *(volatile unsigned*)s->rng_err_host;
-    return IAF_OK;
+    return s->rng.read(errors);
 }
 
 // which packs a prep launch writes for layer L of stack s
-static inline void prep_pack_ptrs(const iaf_stack_t* s, const GemmLayer& L, float** wp, void** wp3, void** wp2, unsigned** rng) {
-    const bool f16 = f16_active(s);
-    *wp2 = f16 ? L.wp2 : nullptr;
-    *rng = f16 ? s->rng_err_dev : nullptr;
-    *wp3 = (f16 && s->skip_bf3_pack) ? nullptr : L.wp3;
-    *wp = (s->skip_f32_pack && L.wp3) ? nullptr : L.wp;
+static inline void stack_prep_packs(const iaf_stack_t* s, const GemmLayer& L, PrepLayer& P) {
+    prep_layer_packs(P, L, pack_prep_writes(*s, PACK_STACK, f16_active(s), L.wp3 != nullptr, s->training), s->rng.dev);
 }
 
 extern "C" int iaf_stack_get_precision(const iaf_stack_t* s, int layer, int B, int H, int W) {
@@ -769,10 +846,9 @@ extern "C" int iaf_stack_prepare(iaf_stack_t* s, const float* const* V, const fl
         PrepLayer& P = a.L[l];
         P.V[0] = V[l]; P.g[0] = g[l]; P.b[0] = b[l];
         if (L.npair == 2) { P.V[1] = V[l + 1]; P.g[1] = g[l + 1]; P.b[1] = b[l + 1]; }
-        prep_pack_ptrs(s, L, &P.wp, &P.wp3, &P.wp2, &P.rng_err);
-        P.bias = L.bias; P.border = L.border; P.variant = s->variant; P.wpt = L.wpt;
-        P.cin = L.cin; P.cout_each = L.cout / L.npair; P.ncot = L.ncot; P.nchunk = L.nchunk;
-        P.zerodiag = L.zerodiag; P.npair = L.npair; P.tile_begin = tiles;
+        stack_prep_packs(s, L, P);
+        prep_layer_geometry(P, L, tiles);
+        P.variant = s->variant;
         tiles += L.ncot;
     }
     const unsigned ff = prep_fast_floats(a.L, a.nlayers);
@@ -790,20 +866,13 @@ extern "C" int iaf_stack_prepare(iaf_stack_t* s, const float* const* V, const fl
 
 // ---- batched prepare: all stacks of a model in ONE launch (weights of every layer are known at step start)
 struct iaf_prep_batch {
-    int n;
-    iaf_stack** stacks;
-    int nlayers_total, ntiles;
-    PrepLayer* h_layers;   // the current descriptor table (host; mutated by every run)
-    DescTable tab;         // its way to the device (pinned snapshots with completion tracking, per-capture tables)
-    int* d_tile2layer;
+    std::vector<iaf_stack*> stacks;
+    BatchTable<PrepLayer> t;       // one descriptor per layer of every stack
 };
 
 extern "C" int iaf_prep_batch_destroy(iaf_prep_batch_t* b) {
     if (!b) return IAF_ERR_NULL;
-    free(b->h_layers);
-    desc_destroy(&b->tab);
-    if (b->d_tile2layer) (void)hipFree(b->d_tile2layer);
-    free(b->stacks);
+    b->t.destroy();
     delete b;
     return IAF_OK;
 }
@@ -812,41 +881,24 @@ extern "C" int iaf_prep_batch_create(iaf_prep_batch_t** out, iaf_stack_t* const*
     if (!out || !stacks) return IAF_ERR_NULL;
     *out = nullptr;
     if (n <= 0) return IAF_ERR_SHAPE;
+    std::vector<int> tiles;
+    for (int i = 0; i < n; ++i) {
+        if (!stacks[i]) return IAF_ERR_NULL;
+        if (stacks[i]->generic) return IAF_ERR_UNSUPPORTED;
+        for (int l = 0; l < stacks[i]->nlayers; ++l) tiles.push_back(stacks[i]->L[l].ncot);
+    }
     iaf_prep_batch* b = new (std::nothrow) iaf_prep_batch();
     if (!b) return (int)hipErrorOutOfMemory;
-    memset(b, 0, sizeof(*b));
-    b->n = n;
-    b->stacks = (iaf_stack**)calloc(n, sizeof(iaf_stack*));
-    int nl = 0, nt = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!stacks[i]) { iaf_prep_batch_destroy(b); return IAF_ERR_NULL; }
-        if (stacks[i]->generic) { iaf_prep_batch_destroy(b); return IAF_ERR_UNSUPPORTED; }
-        b->stacks[i] = stacks[i];
-        for (int l = 0; l < stacks[i]->nlayers; ++l) { nl++; nt += stacks[i]->L[l].ncot; }
-    }
-    b->nlayers_total = nl; b->ntiles = nt;
-    int* t2l = (int*)malloc(sizeof(int) * nt);
-    int rc;
-    b->h_layers = (PrepLayer*)calloc(nl, sizeof(PrepLayer));
-    if (!b->h_layers) { free(t2l); iaf_prep_batch_destroy(b); return (int)hipErrorOutOfMemory; }
-    if ((rc = desc_init(&b->tab, sizeof(PrepLayer) * nl)) != 0 ||
-        (rc = (int)hipMalloc((void**)&b->d_tile2layer, sizeof(int) * nt)) != 0) {
-        free(t2l); iaf_prep_batch_destroy(b); return rc;
-    }
-    int li = 0, tile = 0;
-    for (int i = 0; i < n; ++i)
-        for (int l = 0; l < stacks[i]->nlayers; ++l, ++li) {
-            const GemmLayer& L = stacks[i]->L[l];
-            PrepLayer& P = b->h_layers[li];
-            prep_pack_ptrs(stacks[i], L, &P.wp, &P.wp3, &P.wp2, &P.rng_err);
-            P.bias = L.bias; P.border = L.border; P.variant = stacks[i]->variant; P.wpt = L.wpt;
-            P.cin = L.cin; P.cout_each = L.cout / L.npair; P.ncot = L.ncot; P.nchunk = L.nchunk;
-            P.zerodiag = L.zerodiag; P.npair = L.npair; P.tile_begin = tile;
-            for (int t = 0; t < L.ncot; ++t) t2l[tile++] = li;
+    b->stacks.assign(stacks, stacks + n);
+    if (int rc = b->t.create(tiles, false)) { iaf_prep_batch_destroy(b); return rc; }
+    int li = 0;
+    for (iaf_stack* s : b->stacks)
+        for (int l = 0; l < s->nlayers; ++l, ++li) {
+            PrepLayer& P = b->t.h[li];
+            stack_prep_packs(s, s->L[l], P);
+            prep_layer_geometry(P, s->L[l], b->t.begin[li]);
+            P.variant = s->variant;
         }
-    rc = (int)hipMemcpy(b->d_tile2layer, t2l, sizeof(int) * nt, hipMemcpyHostToDevice);
-    free(t2l);
-    if (rc) { iaf_prep_batch_destroy(b); return rc; }
     *out = b;
     return IAF_OK;
 }
@@ -855,47 +907,39 @@ extern "C" int iaf_prep_batch_run(iaf_prep_batch_t* b, const float* const* V, co
                                   const float* const* bias, void* stream) {
     if (!b || !V || !g || !bias) return IAF_ERR_NULL;
     int li = 0, ci = 0;   // ci: running conv index over all stacks (depth_ar + 2 convs per stack)
-    bool changed = false;
-    for (int i = 0; i < b->n; ++i) {
-        const iaf_stack* s = b->stacks[i];
+    for (const iaf_stack* s : b->stacks) {
         for (int l = 0; l < s->nlayers; ++l, ++li) {
-            PrepLayer& P = b->h_layers[li];
-            const int np = s->L[l].npair;
-            for (int e = 0; e < np; ++e) {
-                if (!V[ci + l + e] || !g[ci + l + e] || !bias[ci + l + e]) return IAF_ERR_NULL;
-                changed |= (P.V[e] != V[ci + l + e]) | (P.g[e] != g[ci + l + e]) | (P.b[e] != bias[ci + l + e]);
-                P.V[e] = V[ci + l + e]; P.g[e] = g[ci + l + e]; P.b[e] = bias[ci + l + e];
-            }
-            changed |= (P.wpt != s->L[l].wpt);       // training switched on/off since the last run
-            P.wpt = s->L[l].wpt;
-            float* wp; void* wp3; void* wp2; unsigned* rng;                            // iaf_stack_set_packs / _set_precision since the last run
-            prep_pack_ptrs(s, s->L[l], &wp, &wp3, &wp2, &rng);
-            changed |= (P.wp != wp) | (P.wp3 != wp3) | (P.wp2 != wp2) | (P.rng_err != rng);
-            P.wp = wp; P.wp3 = wp3; P.wp2 = wp2; P.rng_err = rng;
+            const GemmLayer& L = s->L[l];
+            const float* const* Vl = V + ci + l; const float* const* gl = g + ci + l; const float* const* bl = bias + ci + l;
+            for (int e = 0; e < L.npair; ++e)
+                if (!Vl[e] || !gl[e] || !bl[e]) return IAF_ERR_NULL;
+            b->t.set(li, [&](PrepLayer& P) {
+                for (int e = 0; e < L.npair; ++e) { P.V[e] = Vl[e]; P.g[e] = gl[e]; P.b[e] = bl[e]; }
+                stack_prep_packs(s, L, P);     // iaf_stack_set_packs / _set_precision / _set_training / a range failure since the last run
+            });
         }
         ci += s->depth_ar + 2;
     }
     hipStream_t st = (hipStream_t)stream;
-    // the descriptor table only travels when a pointer in it changed (a training loop passes the same buffers every step)
-    const void* d_layers = nullptr;
-    { int rc = desc_upload(&b->tab, b->h_layers, changed, st, &d_layers); if (rc) return rc; }
+    const PrepLayer* d_layers = nullptr;
+    if (int rc = b->t.upload(st, &d_layers)) return rc;
     // (IAF_PREP_DBG, dev knob: bit 0 = tiles in blockIdx order instead of paired per XCD, bit 1 = round 5's tile function; same box, 20 stacks,
     //  fp16 packs: 13.4 us with both bits, 12.1 us with neither -- profiles/r06/experiments/prep_time_ab_same_box.txt)
     static const int prep_dbg = getenv("IAF_PREP_DBG") ? atoi(getenv("IAF_PREP_DBG")) : 0;
     const int xcdpair = (prep_dbg & 1) ? 0 : 1;
-    const unsigned ff = prep_fast_floats(b->h_layers, b->nlayers_total);
-    hipLaunchKernelGGL(iaf_prep_batch_kernel, dim3(xcdpair ? (b->ntiles + 15) / 16 * 16 : b->ntiles), dim3(256), (size_t)ff * 4, st, (const PrepLayer*)d_layers,
-                       b->d_tile2layer, b->ntiles, xcdpair, ff);
+    const unsigned ff = prep_fast_floats(b->t.h, b->t.n);
+    hipLaunchKernelGGL(iaf_prep_batch_kernel, dim3(xcdpair ? (b->t.ntiles + 15) / 16 * 16 : b->t.ntiles), dim3(256), (size_t)ff * 4, st, d_layers,
+                       b->t.d_tile2layer, b->t.ntiles, xcdpair, ff);
     HIP_TRY(hipGetLastError());
     {
         PackT3Batch tb(st);
-        for (int i = 0; i < b->n; ++i)
-            if (b->stacks[i]->training)
-                for (int l = 0; l < b->stacks[i]->nlayers; ++l) { int rc = tb.add(b->stacks[i]->L[l], NTAPS); if (rc) return rc; }
+        for (const iaf_stack* s : b->stacks)
+            if (s->training)
+                for (int l = 0; l < s->nlayers; ++l) { int rc = tb.add(s->L[l], NTAPS); if (rc) return rc; }
         int rc = tb.flush();
         if (rc) return rc;
     }
-    for (int i = 0; i < b->n; ++i) b->stacks[i]->prepared = true;
+    for (iaf_stack* s : b->stacks) s->prepared = true;
     return IAF_OK;
 }
 
@@ -987,7 +1031,7 @@ static size_t bf3_fused_lds_bytes(int cin, int cin0, int W, int nt, int ppw, int
 }
 // can layer 0 be computed inside layer 1's bf16x3 kernel with this shape?
 static bool fuse_shape_ok(const iaf_stack_t* s, int nt, int ppw, int pxt, int ks, int wco, int W) {
-    if (s->depth_ar < 1 || s->variant != IAF_VARIANT_TF || s->generic || !prec_split(s) || s->skip_bf3_pack) return false;
+    if (s->depth_ar < 1 || s->variant != IAF_VARIANT_TF || s->generic || !prec_split(s) || !(s->packs & IAF_PACK_BF16X3)) return false;
     const GemmLayer& A = s->L[0];
     const GemmLayer& Bl = s->L[1];
     if (!A.wp3 || !Bl.wp3 || A.cin != 32) return false;
@@ -1024,7 +1068,7 @@ static bool auto_shape_bf3(GemmLayer& L, bool is_out, long long P, int W) {
 
 // will a forward launch of this layer run the bf16x3 kernel?  (also fixes L.b_* to the shape it will use)
 static bool bf3_select(const iaf_stack_t* s, GemmLayer& L, int epi, bool negate_taps, bool pix_input, long long P, int W) {
-    if (!prec_split(s) || !L.wp3 || s->skip_bf3_pack) return false;        // (skip_bf3_pack: the bf16x3 pack is not kept up to date)
+    if (!prec_split(s) || !L.wp3 || !(s->packs & IAF_PACK_BF16X3)) return false;        // (iaf_stack_set_packs: the bf16x3 pack is not kept up to date)
     if (negate_taps != (epi == EPI_DGRAD)) return false;           // mirrored taps: the data gradient (transposed bf16x3 pack), only
     if (!(epi == EPI_HIDDEN || ((epi == EPI_OUT || epi == EPI_DGRAD) && pix_input))) return false;
     if (!L.b_user_tuned && L.tuned_P == P && L.tuned_W == W) {       // measured for exactly this problem size
@@ -1051,7 +1095,7 @@ static int launch_gemm(const iaf_stack_t* s, GemmLayer& L, int epi, bool negate_
         bf3 = fn != nullptr;
     }
     if (!bf3 && inmode == IN_FUSED0) return IAF_ERR_UNSUPPORTED;   // (host logic error)
-    if (!bf3 && s->skip_f32_pack && L.wp3) return IAF_ERR_NOT_PREPARED;   // iaf_stack_set_packs: this stack's fp32 pack is not kept up to date
+    if (!bf3 && !(s->packs & IAF_PACK_F32) && L.wp3) return IAF_ERR_NOT_PREPARED;   // iaf_stack_set_packs: this stack's fp32 pack is not kept up to date
     if (!bf3 && !L.user_tuned) auto_shape(L, epi == EPI_OUT, p.P, p.W);
     const int tm = bf3 ? 16 * L.b_ppw * L.b_pxt : 16 * L.pxt;
     const int yg = bf3 ? L.ncot / (L.b_nt * L.b_wco) : L.ncot / (L.nt * L.wco);
@@ -1375,11 +1419,7 @@ static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, co
     }
     // An F16 launch (or the prep of its packs) met an operand beyond fp16's range (its outputs carry inf / NaN): said once, and the stack
     // goes on with the bf16x3 kernels -- behind another prepare where the bf16x3 pack was not being kept up to date.
-    if (s->precision == IAF_PRECISION_F16X2 && !s->f16_off && s->rng_err_host && *(volatile unsigned*)s->rng_err_host) {
-        s->f16_off = true;
-        if (s->skip_bf3_pack) { s->skip_bf3_pack = false; s->prepared = false; }
-        return IAF_ERR_RANGE;
-    }
+    if (pack_range_report(*s, PACK_STACK, s->rng.peek())) return IAF_ERR_RANGE;
     const bool f16 = f16_active(s);
     bool f16_fn = false;                                     // the launch runs an F16 kernel (on the two-plane packs)
     StepP q;
@@ -1455,8 +1495,8 @@ static int launch_fused_step(iaf_stack_t* s, step_fn_t fn, int R, size_t lds, co
     }
     if (f16_fn) {
         for (int l = 0; l < s->nlayers; ++l) q.wp3[l] = s->L[l].wp2;
-        q.rng_err = s->rng_err_dev;
-    } else if (s->skip_bf3_pack) {
+        q.rng_err = s->rng.dev;
+    } else if (!(s->packs & IAF_PACK_BF16X3)) {
         return IAF_ERR_NOT_PREPARED;                         // iaf_stack_set_packs: this stack's bf16x3 pack is not kept up to date
     }
     { int rc = raise_lds_cap((const void*)fn, lds); if (rc) return rc; }
@@ -1601,7 +1641,7 @@ extern "C" int iaf_stack_autotune(iaf_stack_t* s, const float* z, const float* c
         if ((rc = iaf_step_time_layer(s, l, z, context, z_new, logsd, B, H, W, workspace, workspace_bytes, reps, stream, &ms))) break;
         best = ms;
         int bsel[5] = {0, 0, 0, 0, 1};
-        if (saved_prec != IAF_PRECISION_F32 && L.wp3 && !s->skip_bf3_pack && !(is_out && s->depth_ar == 0)) {
+        if (saved_prec != IAF_PRECISION_F32 && L.wp3 && (s->packs & IAF_PACK_BF16X3) && !(is_out && s->depth_ar == 0)) {
             s->precision = IAF_PRECISION_BF16X3;
             const bool ut = L.b_user_tuned;
             const int sv[5] = {L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco};
@@ -1715,25 +1755,11 @@ extern "C" int iaf_stack_autotune(iaf_stack_t* s, const float* z, const float* c
 
 extern "C" int iaf_stack_set_packs(iaf_stack_t* s, int packs) {
     if (!s) return IAF_ERR_NULL;
-    if (packs & ~(IAF_PACK_F32 | IAF_PACK_BF16X3 | IAF_PACK_F16X2)) return IAF_ERR_SHAPE;
-    // the two-plane fp16 pack exists for IAF_PRECISION_F16X2 stacks only -- and only such a stack can do without the bf16x3 pack
-    if ((packs & IAF_PACK_F16X2) && s->precision != IAF_PRECISION_F16X2) return IAF_ERR_UNSUPPORTED;
-    if (!(packs & IAF_PACK_BF16X3) && !((packs & IAF_PACK_F16X2) && !(packs & IAF_PACK_F32) && f16_active(s))) return IAF_ERR_SHAPE;
-    if (!(packs & IAF_PACK_BF16X3) && (s->generic || s->training)) return IAF_ERR_UNSUPPORTED;
-    {
-        const bool skip3 = !(packs & IAF_PACK_BF16X3);
-        if (skip3 != s->skip_bf3_pack) s->prepared = false;
-        s->skip_bf3_pack = skip3;
-    }
-    if (!(packs & IAF_PACK_F32)) {            // only a stack whose every layer has a bf16x3 pack can do without the fp32 one
-        if (s->generic || s->training) return IAF_ERR_UNSUPPORTED;
-        for (int l = 0; l < s->nlayers; ++l)
-            if (!s->L[l].wp3) return IAF_ERR_UNSUPPORTED;
-    }
-    const bool skip = !(packs & IAF_PACK_F32);
-    if (skip != s->skip_f32_pack) s->prepared = false;        // the next prepare brings the pack set up to date
-    s->skip_f32_pack = skip;
-    return IAF_OK;
+    PackFacts f;
+    f.generic = s->generic; f.training = s->training; f.f16_active = f16_active(s);
+    f.all_split = true;            // only a stack whose every layer has a bf16x3 pack can do without the fp32 one
+    for (int l = 0; l < s->nlayers; ++l) f.all_split &= s->L[l].wp3 != nullptr;
+    return pack_stack_set_packs(*s, packs, f);
 }
 
 extern "C" int iaf_stack_set_fuse_step(iaf_stack_t* s, int mode) {
@@ -2068,22 +2094,10 @@ extern "C" int iaf_stack_set_training(iaf_stack_t* s, int on) {
         s->training = true;
         return IAF_OK;
     }
-    for (int l = 0; l < s->nlayers; ++l) {
-        GemmLayer& L = s->L[l];
-        if (!L.wpt) HIP_TRY(hipMalloc(&L.wpt, (size_t)L.nchunk * NTAPS * L.ncot * 256 * sizeof(float)));
-        if (!L.wpt3 && L.ncot % 2 == 0) HIP_TRY(hipMalloc(&L.wpt3, (size_t)(L.ncot / 2) * NTAPS * L.nchunk * 3 * 64 * 16));
-        GemmLayer& T = s->T[l];
-        T = GemmLayer();
-        T.cin = L.cout; T.cout = L.cin; T.nchunk = L.ncot; T.ncot = L.nchunk;
-        T.zerodiag = L.zerodiag; T.npair = 1;
-        T.wp = L.wpt; T.bias = nullptr; T.border = nullptr; T.lim = nullptr; T.wpt = nullptr;
-        T.wp3 = L.wpt3;            // the data gradient runs the bf16x3 kernel where its launch-shape rule takes it (bf3_select)
-        T.nt = 1; T.pxt = 4; T.wco = 1; T.ks = 1; T.user_tuned = false;
-    }
+    for (int l = 0; l < s->nlayers; ++l)
+        if (int rc = gemm_layer_set_training(s->L[l], s->T[l], NTAPS, false)) return rc;
     s->training = true;
-    s->skip_f32_pack = false; // (training keeps every pack: iaf_stack_set_packs refuses training stacks)
-    s->skip_bf3_pack = false;
-    s->prepared = false;      // the transposed packs are written by the next prepare
+    pack_set_training(*s);    // (training keeps every pack: iaf_stack_set_packs refuses training stacks)
     return IAF_OK;
 }
 
@@ -2522,21 +2536,13 @@ extern "C" int iaf_stack_set_defer_weightnorm(iaf_stack_t* s, int on) {
 }
 
 struct iaf_wn_bwd_batch {
-    int n, nconv, ntiles;
-    iaf_stack** stacks;
-    WnBwdLayer* h_layers;   // the current descriptor table (host; mutated by every run)
-    DescTable tab;          // its way to the device (see DescTable)
-    int* d_tile2layer;
-    int* d_tile_begin;
+    std::vector<iaf_stack*> stacks;
+    BatchTable<WnBwdLayer> t;      // one descriptor per conv of every stack, in the conv order of iaf_stack_prepare
 };
 
 extern "C" int iaf_wn_bwd_batch_destroy(iaf_wn_bwd_batch_t* b) {
     if (!b) return IAF_ERR_NULL;
-    free(b->h_layers);
-    desc_destroy(&b->tab);
-    if (b->d_tile2layer) (void)hipFree(b->d_tile2layer);
-    if (b->d_tile_begin) (void)hipFree(b->d_tile_begin);
-    free(b->stacks);
+    b->t.destroy();
     delete b;
     return IAF_OK;
 }
@@ -2545,50 +2551,28 @@ extern "C" int iaf_wn_bwd_batch_create(iaf_wn_bwd_batch_t** out, iaf_stack_t* co
     if (!out || !stacks) return IAF_ERR_NULL;
     *out = nullptr;
     if (n <= 0) return IAF_ERR_SHAPE;
+    std::vector<int> tiles;
+    for (int i = 0; i < n; ++i) {
+        if (!stacks[i]) return IAF_ERR_NULL;
+        if (stacks[i]->generic) return IAF_ERR_UNSUPPORTED;
+        for (int c = 0; c < stacks[i]->depth_ar + 2; ++c)      // output pair: n_z / 16 tiles for each of its two convs
+            tiles.push_back((c < stacks[i]->depth_ar ? stacks[i]->L[c].cout : stacks[i]->n_z) / 16);
+    }
     iaf_wn_bwd_batch* b = new (std::nothrow) iaf_wn_bwd_batch();
     if (!b) return (int)hipErrorOutOfMemory;
-    memset(b, 0, sizeof(*b));
-    b->n = n;
-    b->stacks = (iaf_stack**)calloc(n, sizeof(iaf_stack*));
-    int nconv = 0, nt = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!stacks[i]) { iaf_wn_bwd_batch_destroy(b); return IAF_ERR_NULL; }
-        if (stacks[i]->generic) { iaf_wn_bwd_batch_destroy(b); return IAF_ERR_UNSUPPORTED; }
-        b->stacks[i] = stacks[i];
-        nconv += stacks[i]->depth_ar + 2;
-        for (int l = 0; l < stacks[i]->nlayers; ++l) nt += stacks[i]->L[l].cout / 16;   // output pair: 2 * n_z/16 tiles
-    }
-    b->nconv = nconv; b->ntiles = nt;
-    int* t2l = (int*)malloc(sizeof(int) * nt);
-    int* tb = (int*)malloc(sizeof(int) * (nconv + 1));
-    int rc;
-    b->h_layers = (WnBwdLayer*)calloc(nconv, sizeof(WnBwdLayer));
-    if (!b->h_layers) { free(t2l); free(tb); iaf_wn_bwd_batch_destroy(b); return (int)hipErrorOutOfMemory; }
-    if ((rc = desc_init(&b->tab, sizeof(WnBwdLayer) * nconv)) != 0 ||
-        (rc = (int)hipMalloc((void**)&b->d_tile2layer, sizeof(int) * nt)) != 0 ||
-        (rc = (int)hipMalloc((void**)&b->d_tile_begin, sizeof(int) * (nconv + 1))) != 0) {
-        free(t2l); free(tb); iaf_wn_bwd_batch_destroy(b); return rc;
-    }
-    int ci = 0, tile = 0;
-    for (int i = 0; i < n; ++i) {
-        const iaf_stack* s = stacks[i];
-        for (int c = 0; c < s->depth_ar + 2; ++c, ++ci) {       // conv order of iaf_stack_prepare
+    b->stacks.assign(stacks, stacks + n);
+    if (int rc = b->t.create(tiles, true)) { iaf_wn_bwd_batch_destroy(b); return rc; }
+    int ci = 0;
+    for (const iaf_stack* s : b->stacks)
+        for (int c = 0; c < s->depth_ar + 2; ++c, ++ci) {
             const int l = c < s->depth_ar ? c : s->depth_ar;
             const GemmLayer& L = s->L[l];
-            WnBwdLayer& w = b->h_layers[ci];
+            WnBwdLayer& w = b->t.h[ci];
             const bool pair = (l == s->depth_ar);
             w.cin = L.cin; w.cout = pair ? s->n_z : L.cout; w.cout_packed = L.cout; w.zerodiag = L.zerodiag;
             w.pack_stride = pair ? 2 : 1; w.pack_off = pair ? c - s->depth_ar : 0;
             w.variant = s->variant;
-            tb[ci] = tile;
-            for (int t = 0; t < w.cout / 16; ++t) t2l[tile++] = ci;
         }
-    }
-    tb[ci] = tile;
-    rc = (int)hipMemcpy(b->d_tile2layer, t2l, sizeof(int) * nt, hipMemcpyHostToDevice);
-    if (!rc) rc = (int)hipMemcpy(b->d_tile_begin, tb, sizeof(int) * (nconv + 1), hipMemcpyHostToDevice);
-    free(t2l); free(tb);
-    if (rc) { iaf_wn_bwd_batch_destroy(b); return rc; }
     *out = b;
     return IAF_OK;
 }
@@ -2596,10 +2580,8 @@ extern "C" int iaf_wn_bwd_batch_create(iaf_wn_bwd_batch_t** out, iaf_stack_t* co
 extern "C" int iaf_wn_bwd_batch_run(iaf_wn_bwd_batch_t* b, const float* const* V, const float* const* g, float* const* dV,
                                     float* const* dg, float* const* db, void* stream) {
     if (!b || !V || !g || !dV || !dg || !db) return IAF_ERR_NULL;
-    bool changed = false;
     int ci = 0;
-    for (int i = 0; i < b->n; ++i) {
-        const iaf_stack* s = b->stacks[i];
+    for (const iaf_stack* s : b->stacks) {
         if (!s->defer_wn || !s->pend_ws) return IAF_ERR_NOT_PREPARED;      // no deferred backward pending on this stack
         const long long P = (long long)s->pend_B * s->pend_H * s->pend_W;
         TrainWs tw;
@@ -2608,17 +2590,16 @@ extern "C" int iaf_wn_bwd_batch_run(iaf_wn_bwd_batch_t* b, const float* const* V
         for (int c = 0; c < s->depth_ar + 2; ++c, ++ci) {
             if (!V[ci] || !g[ci] || !dV[ci] || !dg[ci] || !db[ci]) return IAF_ERR_NULL;
             const int l = c < s->depth_ar ? c : s->depth_ar;
-            WnBwdLayer& w = b->h_layers[ci];
-            changed |= (w.V != V[ci]) | (w.g != g[ci]) | (w.dV != dV[ci]) | (w.dg != dg[ci]) | (w.db != db[ci]) |
-                       (w.dW != tw.dWeff[l]) | (w.dbp != tw.dbp[l]) | (w.dbrd != tw.dbrd[l]) | (w.nslab != nslab);
-            w.V = V[ci]; w.g = g[ci]; w.dV = dV[ci]; w.dg = dg[ci]; w.db = db[ci];
-            w.dW = tw.dWeff[l]; w.dbp = tw.dbp[l]; w.dbrd = tw.dbrd[l]; w.nslab = nslab;
+            b->t.set(ci, [&](WnBwdLayer& w) {
+                w.V = V[ci]; w.g = g[ci]; w.dV = dV[ci]; w.dg = dg[ci]; w.db = db[ci];
+                w.dW = tw.dWeff[l]; w.dbp = tw.dbp[l]; w.dbrd = tw.dbrd[l]; w.nslab = nslab;
+            });
         }
     }
     hipStream_t st = (hipStream_t)stream;
-    const void* d_layers = nullptr;
-    { int rc = desc_upload(&b->tab, b->h_layers, changed, st, &d_layers); if (rc) return rc; }
-    hipLaunchKernelGGL(iaf_wn_bwd_batch_kernel, dim3(b->ntiles), dim3(256), 0, st, (const WnBwdLayer*)d_layers, b->d_tile2layer, b->d_tile_begin);
+    const WnBwdLayer* d_layers = nullptr;
+    if (int rc = b->t.upload(st, &d_layers)) return rc;
+    hipLaunchKernelGGL(iaf_wn_bwd_batch_kernel, dim3(b->t.ntiles), dim3(256), 0, st, d_layers, b->t.d_tile2layer, b->t.d_tile_begin);
     return (int)hipGetLastError();
 }
 

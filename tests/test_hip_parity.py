@@ -1041,3 +1041,55 @@ def test_prep_batch_eager_after_a_capture_with_other_tensors(amd):
     ez, es = O.iaf_step(f32(z), f32(ctx), f32_params(pY), [n_h] * d)
     np.testing.assert_allclose(host(z_new), ez, atol=ATOL, rtol=0)
     np.testing.assert_allclose(host(logsd), es, atol=ATOL, rtol=0)
+
+
+def test_conv_batches_eager_after_a_capture_with_other_tensors(amd):
+    """The same sequence on the two batch objects of the plain convs, which share their table code with the stack's: eager(X) ->
+    capture(Y) -> eager(Y) -> eager(X) on a ConvPrepBatch and a WnBwdBatch(convs=...) of one plain conv (32 -> 16 channels, B = 2,
+    8x8).  An eager run that kept the device table of the run before the capture would re-derive the packs from X and write X's
+    gradient tensors; every eager result must equal the un-batched prepare / backward bit for bit."""
+    B, ci, co, H = 2, 32, 16, 8
+    rng = np.random.RandomState(43)
+    x, dy = dev(rng.standard_normal((B, ci, H, H))), dev(rng.standard_normal((B, co, H, H)))
+    vgb = lambda: (dev(0.05 * rng.standard_normal((3, 3, ci, co))), dev(0.1 * rng.standard_normal(co)), dev(0.1 * rng.standard_normal(co)))
+    X, Y = vgb(), vgb()
+    ref = amd.WNConv2d(ci, co)
+    ref.set_training(True)
+
+    def unbatched(p):
+        ref.prepare(*p)
+        y = ref(x)[0]
+        (dx,), dV, dg, db = ref.backward(x, [dy], p[0], p[1])
+        return [t.clone() for t in (y, dx, dV, dg, db)]
+
+    want_X, want_Y = unbatched(X), unbatched(Y)
+    assert not torch.equal(want_X[0], want_Y[0]) and not torch.equal(want_X[2], want_Y[2])
+    conv = amd.WNConv2d(ci, co)
+    conv.set_training(True)
+    prep, wn = amd.ConvPrepBatch([conv]), amd.WnBwdBatch(convs=[conv])
+    gX, gY = [tuple(torch.zeros_like(t) for t in p) for p in (X, Y)]
+
+    def batched(p, grads, want):
+        for t in gX + gY:
+            t.zero_()
+        prep.run([p])
+        y = conv(x)[0]
+        (dx,), _, _, _ = conv.backward(x, [dy], p[0], p[1], grads_out=grads)      # stops before the weight norm (deferred)
+        wn.run(conv_params=[p], conv_grads=[grads])
+        s.synchronize()
+        for got, exp in zip((y, dx) + tuple(grads), want):
+            assert torch.equal(got, exp)
+
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        batched(X, gX, want_X)                                    # eager: the eager device tables hold X
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            prep.run([Y])                                         # captured: the host copies now hold Y, the eager tables still X
+            wn.run(conv_params=[Y], conv_grads=[gY])
+        g.replay()
+        s.synchronize()
+        batched(Y, gY, want_Y)                                    # eager, with the capture's pointers
+        batched(X, gX, want_X)                                    # ... and with another set again
+    torch.cuda.synchronize()
