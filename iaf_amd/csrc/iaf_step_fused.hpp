@@ -217,7 +217,9 @@ struct PairPart {
 // region (R + 1 rows, 11.5 KB) through device memory with the machinery of XCH: tickets (partners hold adjacent tickets of one list, so
 // at most one workgroup per list ever waits for a partner that is not running yet), the data as the flag, helper waves.  The output
 // pair multiplies the input channels of its own half first -- they are in LDS already -- and the partner's behind the import.
-template <int NHT, int NZT, int DEPTH, int W, int R, int VAR = 0, int XCH = 0, int HLP = XCH, int PAIR = 0, int F16 = 0>
+// FLAT = 1 (the fp16-plane instantiations): the hidden epilogues and the final loop without per-unit branches -- see hidden_epilogue and
+// "affine transform" below.  The same arithmetic on the same values: results are bit-identical to FLAT = 0.
+template <int NHT, int NZT, int DEPTH, int W, int R, int VAR = 0, int XCH = 0, int HLP = XCH, int PAIR = 0, int F16 = 0, int FLAT = 0>
 __global__ __launch_bounds__(HLP ? 512 : 256)
 __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fused_kernel(StepP p) {
     static_assert(HLP || !XCH, "the exchange form runs with helper waves");
@@ -860,6 +862,48 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
 #pragma unroll
                     for (int r = 0; r < 4; ++r) cxv[q][j][r] = cr[r * G::CSTR];
                 }
+        }
+        if constexpr (FLAT) {
+            // One scheduling region: a unit that is its own basic block (the three `continue`s below, each an exec-mask branch) is a serial
+            // chain acc -> +bias -> +ctx -> ELU -> split -> ds_write that nothing can be interleaved with.  Here every test is either
+            // compile time or a select:
+            //   tile past the layer   cannot happen where the left-over tiles are dealt out per pixel tile (or there are none);
+            //   lane past the tile    conv_phase clamps such a lane's pixel to the last one, so its accumulator EQUALS that pixel's: with the
+            //                         slot clamped alike it stores the same bytes to the same place once more;
+            //   row past the image    a select on the value, as before.
+            // The training stores (hsave, a uniform pointer) follow in a block of their own.
+            static_assert(XSPLIT || NX == 0, "FLAT: every tile slot holds a tile of the layer");
+            f32x4 vout[NTWH][NPT];
+            static_for<NTWH * NPT>([&](auto oi_c) {
+                constexpr int j = decltype(oi_c)::value / NPT, q = decltype(oi_c)::value % NPT;
+                if constexpr (j != NTWH - 1 || ((EMASK >> q) & 1)) {
+                    int pix = (q + qbase) * 16 + pl;
+                    pix = pix < ROWS * W ? pix : ROWS * W - 1;
+                    const int row = pix / W, col = pix - row * W;
+                    f32x4 v = acc[q][j] + bias[j];
+                    if constexpr (BORDER) { if (r0 + row < H) v += border_terms(bt, NH, htile[j] * 16 + 4 * kk, r0 + row, col); }   // conv.py:71-83
+                    if constexpr (WITH_CTX) v += cxv[q][j];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = elu_f(v[r]);
+                    const bool below = r0 + row >= H;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = below ? 0.f : v[r];
+                    split_store4(smem + (size_t)out_reg * 16, row * RS + col + 1, htile[j] * 4 + kk, v, H16, H8);
+                    vout[j][q] = v;
+                }
+            });
+            if (hsave) {     // training: the rows this workgroup OWNS (not its halo) go to HBM for the backward pass
+                static_for<NTWH * NPT>([&](auto oi_c) {
+                    constexpr int j = decltype(oi_c)::value / NPT, q = decltype(oi_c)::value % NPT;
+                    if constexpr (j != NTWH - 1 || ((EMASK >> q) & 1)) {
+                        const int pix = (q + qbase) * 16 + pl;
+                        const int row = pix / W, col = pix - row * W;
+                        if (pix < ROWS * W && row < R && r0 + row < H && (!save_half || (htile[j] >= NHT / 2) == (half != 0)))
+                            *(f32x4*)(hsave + ((size_t)b * HW + (size_t)gpix(r0 + row, col)) * NH + htile[j] * 16 + 4 * kk) = vout[j][q];
+                    }
+                });
+            }
+            return;
         }
 #pragma unroll
         for (int oi = 0; oi < NTWH * NPT; ++oi) {
@@ -1671,6 +1715,109 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
 #pragma unroll
     for (int e = 0; e < NEL; ++e) klv[e] = 0.f;
     const int fcb = PAIR ? half * NZF : 0;
+    if constexpr (FLAT) {
+        // The loop below decides the mode per element and skips elements with `continue`: every element is a chain of basic blocks of its
+        // own -- exchange-buffer reads, a wait, the arithmetic, the stores, one round trip after another.  Here: the exchange-buffer operands
+        // of ALL elements first (one wait for the lot), then one loop body per mode behind a single uniform dispatch, with the stores alone
+        // predicated.  The sums and the arithmetic are the loop's below, term for term.
+        float mr[NEL], sr[NEL];
+        unsigned gio[NEL];
+        bool live[NEL];
+#pragma unroll
+        for (int e = 0; e < NEL; ++e) {
+            const int idx = tid + e * 256;
+            const int ic = idx < NZF * R * W ? idx : NZF * R * W - 1;              // (as load_final_operands: a valid address either way)
+            const int c = fcb + ic / (R * W), pix = ic % (R * W);
+            const int row = pix / W, col = pix - row * W;
+            live[e] = idx < NZF * R * W && r0 + row < H;
+            const int rr = r0 + row < H ? r0 + row : H - 1;
+            gio[e] = 4u * (unsigned)(c * HW + gpix(rr, col));                      // byte offset inside image b
+            const int cm = (c >> 4) * 32 + (c & 15);
+            float m_raw = fb[e][0], s_raw = fb[e][1];
+            if constexpr (BORDER) {                                                // the border channel of the output pair's own input
+                const float* bt = p.border[DEPTH];
+                const bool last_row = r0 + row == H - 1, c0 = col == 0, cl = col == W - 1;
+                const float w1 = cl ? 1.f : 0.f, w2 = (last_row || c0) ? 1.f : 0.f, w3 = last_row ? 1.f : 0.f, w4 = (last_row || cl) ? 1.f : 0.f;
+                m_raw += w1 * bt[cm] + w2 * bt[2 * NZ + cm] + w3 * bt[4 * NZ + cm] + w4 * bt[6 * NZ + cm];
+                s_raw += w1 * bt[cm + 16] + w2 * bt[2 * NZ + cm + 16] + w3 * bt[4 * NZ + cm + 16] + w4 * bt[6 * NZ + cm + 16];
+            }
+            const float x0 = xbuf[pix * G::XB_STRIDE + cm], x1 = xbuf[pix * G::XB_STRIDE + cm + 16];
+            m_raw += x0; s_raw += x1;
+            if constexpr (XK2) {                                                   // (the other K part)
+                const float y0 = xbuf[(R * W + pix) * G::XB_STRIDE + cm], y1 = xbuf[(R * W + pix) * G::XB_STRIDE + cm + 16];
+                m_raw += y0; s_raw += y1;
+            }
+            mr[e] = m_raw; sr[e] = s_raw;
+        }
+        // The arithmetic with its roundings written out (no contraction left to the compiler: which products it fuses into the following
+        // add depends on how the code around them is laid out, and the results are to be those of the loop below, bit for bit):
+        //   IAF        (z - 0.1 m) e^-s      = e^-s * fma(m, -0.1, z)
+        //   inverse    z e^s + 0.1 m         = (z * e^s) + (0.1 * m), each product rounded
+        //   posterior  z0 = fma(e^(logvar/2), eps, mean);  logqs = fma(-0.5, fma(e^-logvar, d0^2, c + logvar), s);
+        //              kl = fma(0.5, fma(e^-plv, d1^2, c + plv), logqs)
+        auto mul_r = [](float x, float y) __attribute__((always_inline)) -> float {
+#pragma clang fp contract(off)
+            return x * y;
+        };
+        auto add_r = [](float x, float y) __attribute__((always_inline)) -> float {
+#pragma clang fp contract(off)
+            return x + y;
+        };
+        constexpr float LOG2PI = 1.8378770664093453f;
+        const int mode = p.mode;
+        if (mode == MODE_RAW) {
+#pragma unroll
+            for (int e = 0; e < NEL; ++e)
+                if (live[e]) { stf(p.out0 + img_z, gio[e], mr[e]); stf(p.out1 + img_z, gio[e], sr[e]); }
+        } else if (mode == MODE_IAF) {
+            float o0[NEL], o1[NEL];
+#pragma unroll
+            for (int e = 0; e < NEL; ++e) {
+                const float s = mul_r(sr[e], 0.1f);                                // tf_train.py:70
+                o0[e] = mul_r(__builtin_fmaf(mr[e], -0.1f, fz[e]), __expf(-s));    // tf_train.py:71 (x * exp(-s): see below)
+                o1[e] = s;                                                         // tf_train.py:72
+            }
+#pragma unroll
+            for (int e = 0; e < NEL; ++e)
+                if (live[e]) { stf(p.out0 + img_z, gio[e], o0[e]); stf(p.out1 + img_z, gio[e], o1[e]); }
+        } else if (mode == MODE_INVERSE) {
+            float o0[NEL], o1[NEL];
+#pragma unroll
+            for (int e = 0; e < NEL; ++e) {
+                const float m = mul_r(mr[e], 0.1f), s = mul_r(sr[e], 0.1f);
+                o0[e] = add_r(mul_r(fz[e], __expf(s)), m);
+                o1[e] = s;
+            }
+#pragma unroll
+            for (int e = 0; e < NEL; ++e)
+                if (live[e]) { stf(p.out0 + img_z, gio[e], o0[e]); stf(p.out1 + img_z, gio[e], o1[e]); }
+        } else {
+            float o0[NEL], o1[NEL], kv[NEL];
+#pragma unroll
+            for (int e = 0; e < NEL; ++e) {
+                const float s = mul_r(sr[e], 0.1f);
+                const float mean = fq[e][0];                                                          // tf_train.py:57
+                const float logvar = add_r(fq[e][1], fq[e][1]);
+                const float z0 = __builtin_fmaf(__expf(mul_r(0.5f, logvar)), fq[e][2], mean);         // :63
+                const float d0 = add_r(z0, -mean);
+                const float logqs = __builtin_fmaf(-0.5f, __builtin_fmaf(__expf(-logvar), mul_r(d0, d0), add_r(LOG2PI, logvar)), s);   // :68, :72
+                const float zz = mul_r(__builtin_fmaf(mr[e], -0.1f, z0), __expf(-s));                 // :71
+                const float plv = add_r(fq[e][4], fq[e][4]);                                          // :56
+                const float d1 = add_r(zz, -fq[e][3]);
+                o0[e] = zz; o1[e] = s;
+                kv[e] = __builtin_fmaf(0.5f, __builtin_fmaf(__expf(-plv), mul_r(d1, d1), add_r(LOG2PI, plv)), logqs);                  // :73, :75
+            }
+#pragma unroll
+            for (int e = 0; e < NEL; ++e)
+                if (live[e]) {
+                    stf(p.out0 + img_z, gio[e], o0[e]);
+                    if (p.out1) stf(p.out1 + img_z, gio[e], o1[e]);
+                    if (p.kl_elem) stf(p.kl_elem + img_z, gio[e], kv[e]);
+                }
+#pragma unroll
+            for (int e = 0; e < NEL; ++e) klv[e] = live[e] ? kv[e] : 0.f;
+        }
+    } else {
 #pragma unroll
     for (int e = 0; e < NEL; ++e) {
         const int idx = tid + e * 256;
@@ -1724,6 +1871,7 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
             klv[e] = logqs - logps;                                                               // :75
             if (p.kl_elem) stf(p.kl_elem + img_z, gi, klv[e]);
         }
+    }
     }
     // ---- the block's KL reductions start here (tf_train.py:77, sum over H, W): a channel's R*W pixels are R*W consecutive
     // lanes of one wave -> butterfly sum, one 4-byte store per (row block, channel); see StepP::kl_part

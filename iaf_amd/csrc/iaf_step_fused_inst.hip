@@ -161,6 +161,7 @@ static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
 
 // the two-plane fp16 kernels (round 6, "f16x2": three part-products per K step instead of six): the BASELINE run's geometries, TF
 // statement -- 16-pixel rows in the exchange form (form 1), 8-pixel rows recomputing with helper waves (form 0) -- and config 3's
+// (all of them with the branch-free epilogues and final loop, FLAT = 1: the headline runs on these)
 template <int NHT, int NZT, int DEPTH, int W, int R, int XCH>
 static step_fn_t inst_f16(int var, size_t* lds, size_t* xrow) {
     typedef StepGeom<NHT, NZT, DEPTH, W, R, XCH, 0, 1> G;
@@ -171,9 +172,9 @@ static step_fn_t inst_f16(int var, size_t* lds, size_t* xrow) {
     *lds = G::lds_bytes();
     if (xrow) *xrow = XCH ? G::xrow_bytes() : 0;
     switch (var) {
-        case 0: return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 0, XCH, 1, 0, 1>;
-        case 1: return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 1, XCH, 1, 0, 1>;
-        case 2: return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 2, XCH, 1, 0, 1>;
+        case 0: return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 0, XCH, 1, 0, 1, 1>;
+        case 1: return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 1, XCH, 1, 0, 1, 1>;
+        case 2: return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 2, XCH, 1, 0, 1, 1>;
     }
     return nullptr;
 }
@@ -185,7 +186,7 @@ static step_fn_t inst_f16_tf(int var, size_t* lds, size_t* xrow) {
     if (var != 0) return nullptr;
     *lds = G::lds_bytes();
     if (xrow) *xrow = XCH ? G::xrow_bytes() : 0;
-    return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 0, XCH, 1, 0, 1>;
+    return iaf_step_fused_kernel<NHT, NZT, DEPTH, W, R, 0, XCH, 1, 0, 1, 1>;
 }
 #if IAF_FUSED_PART == 5
 static step_fn_t pick(const StepKey& k, size_t* lds, size_t* row) {
