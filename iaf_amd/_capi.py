@@ -202,6 +202,12 @@ SIGNATURES = {
     "iaf_rng_seek": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
     "iaf_rng_skip": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
     "iaf_rng_tell": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), _vp]),
+    "iaf_data_create": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int]),
+    "iaf_data_destroy": (ctypes.c_int, [_vp]),
+    "iaf_data_next_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "iaf_data_seek": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
+    "iaf_data_skip": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
+    "iaf_data_tell": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), _vp]),
     "iaf_conv3x3_work": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 2),
 }
 

@@ -32,6 +32,7 @@
 //   iaf_kernels_generic.hpp   direct-conv fallback for channel counts outside the MFMA path
 //   iaf_kernels_resample.hpp  2x resampling and the deconv2d weight prep (downsampling IAFLayer)
 //   iaf_kernels_rng.hpp       the device noise source: Philox4x32-10 normals for a list of tensors in one launch
+//   iaf_kernels_data.hpp      the device-resident dataset: one launch gathers the next shuffled batch (keyed Feistel permutation)
 //   (this file)               stack object, launch logic, C ABI of the masked stack, forward / inverse / training
 //   iaf_conv3x3_host.hpp      C ABI of the plain and single masked 3x3 convs, init, likelihood
 //   iaf_model_edge.hpp        the two ends of the model around the layer stack (CVAE1._forward: x_enc, h_top, x_dec, obj / loss)
@@ -65,6 +66,7 @@
 #include "iaf_kernels_generic.hpp"
 #include "iaf_kernels_resample.hpp"
 #include "iaf_kernels_rng.hpp"
+#include "iaf_kernels_data.hpp"
 
 #include "iaf_pack_state.hpp"   // the pack / precision / range protocol of iaf_stack and iaf_conv3x3 (no HIP in it: walked on a CPU by tests/test_pack_state.py)
 
@@ -2885,6 +2887,103 @@ extern "C" int iaf_rng_tell(iaf_rng_t* r, uint64_t* step, void* stream) {
     if (cs == hipStreamCaptureStatusActive) return (int)hipErrorStreamCaptureUnsupported;
     unsigned long long v = 0;
     hipError_t e = hipMemcpyAsync(&v, r->d_step, sizeof(v), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    *step = v;
+    return IAF_OK;
+}
+
+// the device-resident dataset (iaf_kernels_data.hpp): images borrowed from the caller, seed and flag here, the 64-bit step counter in device
+// memory like the noise source's -- the gather reads it, a one-thread launch behind it advances it, a replayed hipGraph gathers the next batch
+struct iaf_data {
+    const unsigned char* images = nullptr;
+    unsigned long long n = 0, bpi = 0, seed = 0;
+    int deterministic = 0;
+    unsigned long long* d_step = nullptr;
+};
+
+extern "C" int iaf_data_create(iaf_data_t** out, const unsigned char* images, uint64_t n, size_t bytes_per_image, uint64_t seed,
+                               int deterministic) {
+    if (!out) return IAF_ERR_NULL;
+    *out = nullptr;
+    if (!images) return IAF_ERR_NULL;
+    if (n == 0 || n >= (1ull << 32) || bytes_per_image == 0) return IAF_ERR_SHAPE;
+    iaf_data_t* d = new (std::nothrow) iaf_data_t();
+    if (!d) return (int)hipErrorOutOfMemory;
+    d->images = images;
+    d->n = n;
+    d->bpi = bytes_per_image;
+    d->seed = seed;
+    d->deterministic = deterministic != 0;
+    hipError_t e = hipMalloc((void**)&d->d_step, 64);
+    if (e == hipSuccess) e = hipMemset(d->d_step, 0, 64);
+    if (e != hipSuccess) {
+        if (d->d_step) (void)hipFree(d->d_step);
+        delete d;
+        return (int)e;
+    }
+    *out = d;
+    return IAF_OK;
+}
+
+extern "C" int iaf_data_destroy(iaf_data_t* d) {
+    if (!d) return IAF_OK;
+    if (d->d_step) (void)hipFree(d->d_step);
+    delete d;
+    return IAF_OK;
+}
+
+extern "C" int iaf_data_next_batch(iaf_data_t* d, unsigned char* out, long long* idx_out, int B, int rank, int world, int advance,
+                                   void* stream) {
+    if (!d || !out) return IAF_ERR_NULL;
+    if (B < 1 || B > IAF_DATA_MAX_BATCH || world < 1 || rank < 0 || rank >= world) return IAF_ERR_SHAPE;
+    const unsigned long long G = (unsigned long long)B * (unsigned long long)world;
+    if (G > d->n) return IAF_ERR_SHAPE;
+    const unsigned long long slices = (d->bpi + IAF_DATA_SLICE - 1) / IAF_DATA_SLICE;
+    if (slices > 0x7fffffffull) return IAF_ERR_SHAPE;
+    IafDataDraw D;
+    memset(&D, 0, sizeof(D));
+    D.bpi = d->bpi;
+    D.n = (unsigned)d->n;
+    D.G = (unsigned)G;
+    D.bpe = (unsigned)(d->n / G);
+    D.first = (unsigned)rank * (unsigned)B;
+    unsigned bits = 0;                                                  // bitlength(n - 1)
+    for (unsigned long long v = d->n - 1; v; v >>= 1) ++bits;
+    D.w = bits < 2 ? 1u : (bits + 1) / 2;
+    D.k0 = (unsigned)(d->seed & 0xffffffffull) ^ 0x61746164u;
+    D.k1 = (unsigned)(d->seed >> 32) ^ 0x5F666169u;
+    D.deterministic = d->deterministic;
+    D.vec16 = d->bpi % 16 == 0 && (((uintptr_t)d->images | (uintptr_t)out) & 15) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(iaf_data_gather_kernel, dim3((unsigned)slices, (unsigned)B), dim3(256), 0, st, d->images, out, idx_out,
+                       (const unsigned long long*)d->d_step, D);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !advance) return (int)e;
+    hipLaunchKernelGGL(iaf_rng_step_kernel, dim3(1), dim3(1), 0, st, d->d_step, 1ull, 1);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_data_seek(iaf_data_t* d, uint64_t step, void* stream) {
+    if (!d) return IAF_ERR_NULL;
+    hipLaunchKernelGGL(iaf_rng_step_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d->d_step, (unsigned long long)step, 0);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_data_skip(iaf_data_t* d, uint64_t steps, void* stream) {
+    if (!d) return IAF_ERR_NULL;
+    hipLaunchKernelGGL(iaf_rng_step_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d->d_step, (unsigned long long)steps, 1);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_data_tell(iaf_data_t* d, uint64_t* step, void* stream) {
+    if (!d || !step) return IAF_ERR_NULL;
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st) (void)hipStreamIsCapturing(st, &cs);
+    if (cs == hipStreamCaptureStatusActive) return (int)hipErrorStreamCaptureUnsupported;
+    unsigned long long v = 0;
+    hipError_t e = hipMemcpyAsync(&v, d->d_step, sizeof(v), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return (int)e;
     *step = v;

@@ -69,7 +69,7 @@ def _range_objects(model):
 
 
 class TrainStep(object):
-    """ts = TrainStep(model, lr); obj = ts(x, noise) per batch.
+    """ts = TrainStep(model, lr); obj = ts(x, noise) per batch (ts(x) with a noise_source, ts() with a dataset as well).
 
     model: a CVAE1 after set_training(True) and load(params).  The constructor lays its variables out in ONE flat buffer in
     model.completion_order() (ts.flat: params, grads, slots, EMA; the model is re-loaded with the views of ts.flat.p), cuts the
@@ -91,6 +91,14 @@ class TrainStep(object):
     recovery) run on what the buffers hold and never advance the source.  ts(x, noise) with a list still works: that call runs as eager
     launches on the list and moves the source on by one like any other call.
 
+    data (a DeviceDataset; device parameters only) with batch_size: ts() takes no batch -- the step gathers its own, one launch into a
+    uint8 [batch_size,3,S,S] buffer the step owns, the FIRST launch of the step (in front of the noise draw), in graph mode inside the
+    captured graph: nothing is copied into the graph's inputs before a replay, and a replay trains on the next shuffled batch.  The rules
+    are the noise source's: the buffer is filled once WITHOUT advancing the dataset when it is created, the compute-only passes run on
+    what it holds, and call t trains on step s0 + t of the dataset whatever was skipped or captured again.  ts(x) with an explicit batch
+    still works: that call runs as eager launches on x and moves the dataset on by one.  Without a noise_source, ts(noise=list).  The
+    dataset is built with this rank's rank and the step's world.
+
     summaries=True: the step also produces the numbers the reference loop fetches and logs (tf_train.py:142, 148-149, 203-204,
     214-216, 268-285) -- with launches of the step itself (in graph mode inside the captured graph) that accumulate in device memory,
     so no step waits for the host.  The model's fb_begin must take terms=True and return "terms" (CVAE1 does), and the model needs
@@ -108,7 +116,7 @@ class TrainStep(object):
     _FIXED = ("model/bits_per_dim", "model/dec_log_stdv", "model/log_pxz", "model/kl_obj", "model/kl_cost", "grad_norm")
 
     def __init__(self, model, lr, n_buckets=1, comm=None, graph=True, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.999,
-                 noise_source=None, summaries=False):
+                 noise_source=None, summaries=False, data=None, batch_size=None):
         if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0:
             raise ValueError("lr must be a positive finite number, got %r" % (lr,))
         if isinstance(n_buckets, bool) or not isinstance(n_buckets, int) or n_buckets < 1:
@@ -122,6 +130,15 @@ class TrainStep(object):
             raise ValueError("eps must be a finite number >= 0, got %r" % (eps,))
         if not isinstance(summaries, bool):
             raise ValueError("summaries must be True or False, got %r" % (summaries,))
+        if data is not None:
+            from .data import DeviceDataset
+            if not isinstance(data, DeviceDataset):
+                raise ValueError("data must be a DeviceDataset, got %r" % (data,))
+            if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+                raise ValueError("TrainStep(data=): batch_size must be a positive int, got %r" % (batch_size,))
+            data.batches_per_epoch(batch_size)          # (ValueError: a global batch larger than the dataset)
+        elif batch_size is not None:
+            raise ValueError("TrainStep: batch_size goes with data=")
         if getattr(model, "params", None) is None:
             raise RuntimeError("TrainStep: model.set_training(True), then model.load(params), first")
         if summaries:
@@ -143,7 +160,11 @@ class TrainStep(object):
             raise ValueError("TrainStep: graph=True needs device parameters")
         if noise_source is not None and not self.on_device:
             raise ValueError("TrainStep: noise_source needs device parameters (host replicas take their noise from the caller)")
+        if data is not None and not self.on_device:
+            raise ValueError("TrainStep: data needs device parameters (host replicas take their batches from the caller)")
         self.noise_source = noise_source
+        self.data, self.batch_size = data, batch_size
+        self._xb = None                   # the batch buffer a dataset fills
         self._drawn = None                # the posterior noise buffers a source fills (forward()'s layout, None in the prior slots)
         model.load(self.flat.p)
         names = model.set_grad_buckets(n_buckets)
@@ -153,6 +174,8 @@ class TrainStep(object):
         self.world = 1
         if self.red.active:
             self.world = int(getattr(self.red.comm, "world", 0) or dist.get_world_size())
+        if data is not None and data.world != self.world:
+            raise ValueError("TrainStep: the dataset was built for a world of %d, the step has %d" % (data.world, self.world))
         # the reference's towers inside this rank's batch (CVAE1(towers=N), tf_train.py:124-147): the gradients are sums over world * towers
         # towers, which average_grads divides by their number
         self.towers = check_groups(getattr(model, "towers", 1), "model.towers")
@@ -173,6 +196,7 @@ class TrainStep(object):
         self.captures = 0
         self._graph = None
         self._static = None
+        self._static_gathers = False      # the captured step begins with the dataset's gather
         self._stale = False               # the captured graph must be captured again before its next replay
         self._stream = torch.cuda.Stream(device=dev) if graph else None
         self.with_summaries = summaries
@@ -199,11 +223,14 @@ class TrainStep(object):
         self._status[1:2].copy_(self._terms["loss"].reshape(1))
         return fb
 
-    def _enqueue(self, x, noise, draw=False):
-        """one whole step on the current stream; returns the objective.  draw: `noise` is the step's own buffer set, and the step's
-        first launch fills it from the noise source (one step of the source)"""
+    def _enqueue(self, x, noise, draw=False, gather=False):
+        """one whole step on the current stream; returns the objective.  gather: `x` is the step's own batch buffer, and the step's first
+        launch fills it from the dataset (one step of the dataset).  draw: `noise` is the step's own buffer set, and the launch behind
+        that fills it from the noise source (one step of the source)"""
         m, red, flat = self.model, self.red, self.flat
         sent, status_sent = 0, False
+        if gather:
+            self.data.next_batch(self.batch_size, out=x)
         if draw:
             m.draw_noise(int(x.shape[0]), self.noise_source, which="posterior", out=noise)
         try:
@@ -353,7 +380,7 @@ class TrainStep(object):
                 g = torch.cuda.CUDAGraph()
                 try:
                     with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                        obj = self._enqueue(x, noise, draw=self.noise_source is not None)
+                        obj = self._enqueue(x, noise, draw=self.noise_source is not None, gather=self._static_gathers)
                 except _SWITCHED:
                     torch.cuda.synchronize()
                     continue
@@ -379,17 +406,31 @@ class TrainStep(object):
             self._drawn = self.model.draw_noise(B, self.noise_source, which="posterior", advance=False)
         return self._drawn
 
-    def __call__(self, x, noise=None):
-        src = self.noise_source
+    def _own_batch(self):
+        """the batch buffer the dataset fills; filled once WITHOUT advancing the dataset when it is created, so that a compute-only pass
+        before the first step has a batch to run on"""
+        if self._xb is None:
+            self._xb = self.data.next_batch(self.batch_size, advance=False)
+        return self._xb
+
+    def __call__(self, x=None, noise=None):
+        src, data = self.noise_source, self.data
+        if x is None and data is None:
+            raise ValueError("TrainStep: pass the step's batch, or build the step with data=")
         if noise is None and src is None:
             raise ValueError("TrainStep: pass the step's noise list, or build the step with noise_source=")
-        draw = noise is None
+        draw, gather = noise is None, x is None
+        if gather:
+            x = self._own_batch()
         moved = self._must_move() or self._stale
         self._stale = False
-        # (a step built with a source captures the draw into its graph: a call that brings its own list runs as eager launches)
-        if self.use_graph and self.graph_refused is None and (draw or src is None):
+        # (a step built with a source captures the draw into its graph: a call that brings its own list runs as eager launches; so does
+        #  a call that brings its own batch to a step built with a dataset)
+        if self.use_graph and self.graph_refused is None and (draw or src is None) and (gather or data is None):
             if self._static is None:
-                self._static = (x.clone(), self._own_noise(x) if draw else [None if e is None else e.clone() for e in noise])
+                self._static = (x if gather else x.clone(),
+                                self._own_noise(x) if draw else [None if e is None else e.clone() for e in noise])
+                self._static_gathers = gather
                 moved = True
             else:
                 sx, sn = self._static
@@ -397,7 +438,8 @@ class TrainStep(object):
                     raise ValueError("TrainStep(graph=True): x and noise must keep the shapes of the first call")
                 if not draw and (len(noise) != len(sn) or any((a is None) != (b is None) or (a is not None and a.shape != b.shape) for a, b in zip(noise, sn))):
                     raise ValueError("TrainStep(graph=True): x and noise must keep the shapes of the first call")
-                sx.copy_(x)
+                if not gather:
+                    sx.copy_(x)
                 if not draw:
                     for a, b in zip(sn, noise):
                         if a is not None:           # (a slot the model does not read may be None, as CVAE1.forward allows)
@@ -412,9 +454,11 @@ class TrainStep(object):
         if moved:
             self._move(x, noise)
             self._stale = self._graph is not None        # objects switched kernels outside the graph: capture it again before its next replay
-        obj = self._enqueue(x, noise, draw=draw)
+        obj = self._enqueue(x, noise, draw=draw, gather=gather)
         if src is not None and not draw:
             src.skip(1)
+        if data is not None and not gather:
+            data.skip(1)
         return obj
 
     @property

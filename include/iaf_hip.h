@@ -790,6 +790,52 @@ int iaf_rng_seek(iaf_rng_t* r, uint64_t step, void* stream);
 int iaf_rng_skip(iaf_rng_t* r, uint64_t steps, void* stream);
 int iaf_rng_tell(iaf_rng_t* r, uint64_t* step, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The device-resident dataset.  The reference keeps its whole training set in the graph and every step pulls a shuffled batch out of
+ * it (tf_utils/cifar10_data.py:108-112, tf_utils/data_utils.py:29-36); iaf_data_t is that source for an image array the caller
+ * holds in device memory: ONE launch gathers the next batch, and what it gathers depends on (seed, step, row) and on nothing else.
+ *
+ * Definition.  n images of bytes_per_image bytes each, contiguous (uint8 [n,3,S,S]), 1 <= n < 2^32.  A draw has a local batch B, a
+ * rank and a world; G = B * world <= n rows make one global batch and bpe = n / G (integer division) batches make one epoch: the
+ * remainder is dropped and the next epoch reshuffles.  At step t (the 64-bit counter):
+ *     e = t / bpe;   row r of the batch holds slot j = (t % bpe) * G + rank * B + r;   its image is perm_e(j)   (deterministic: j)
+ * perm_e is a keyed bijection of [0, n): a 4-round balanced Feistel network with cycle walking whose round function is the
+ * Philox4x32-10 above.
+ *     n == 1: perm_e(j) = 0.   Else w = max(1, ceil(bitlength(n - 1) / 2)), mask = 2^w - 1,
+ *     key = ((seed & 0xffffffff) ^ 0x61746164, (seed >> 32) ^ 0x5F666169)      (a noise source of the same seed shares no stream)
+ *     one pass on y:   L = y >> w, R = y & mask;
+ *                      for r = 0..3:  (L, R) = (R, L ^ (philox(ctr = (R, r, e & 0xffffffff, e >> 32), key)[0] & mask));
+ *                      y = (L << w) | R
+ *     perm_e(j): start from y = j and repeat the pass while y >= n.
+ * The walk ends: j < n lies on a cycle of the permutation of [0, 4^w), and that cycle returns to j itself; there is no iteration
+ * cap (a cap would break the bijection).  4^w < 4n, so fewer than 4 passes are expected.  This is a keyed pseudo-random permutation,
+ * not a uniform draw from the n! orders (for tiny n the orders are visibly uneven).  tests/data_reference.py states it in numpy.
+ *
+ * iaf_data_create: `images` is BORROWED -- device memory the caller keeps alive and unchanged while the handle is used; no copy.
+ *   The handle holds the seed and the flag on the host and a 64-bit STEP COUNTER IN DEVICE MEMORY (0 after create).
+ * iaf_data_next_batch: ONE launch (grid ceil(bytes_per_image / 4096) x B) copies the B images of `rank` at the counter's step into
+ *   out [B * bytes_per_image bytes, device]; 16-byte loads and stores when bytes_per_image % 16 == 0 and both `images` and `out` lie
+ *   on a 16-byte boundary, bytes otherwise.  idx_out (device int64 [B], may be NULL) receives the image indices.  No upload, no host
+ *   synchronisation, capturable; the launch READS the step from device memory and advance != 0 enqueues a one-thread launch behind
+ *   it that adds 1, so a replayed hipGraph that holds such a call gathers the next batch on every replay.  advance = 0 leaves the
+ *   counter alone (the same batch again next time).  Ranks pass the same seed and B and take disjoint rows without talking.
+ * iaf_data_seek / iaf_data_skip / iaf_data_tell: as iaf_rng_seek / iaf_rng_skip / iaf_rng_tell (tell SYNCHRONISES the stream and is
+ *   refused during a capture with hipErrorStreamCaptureUnsupported).
+ * One dataset is driven from one stream at a time (the counter is ordered by the stream).
+ * Errors, before any device work: IAF_ERR_NULL (out, handle, images, step); IAF_ERR_SHAPE (n = 0 or n >= 2^32, bytes_per_image = 0,
+ * B < 1 or B > IAF_DATA_MAX_BATCH (the launch's second grid dimension), world < 1, rank outside [0, world), B * world > n).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct iaf_data iaf_data_t;
+#define IAF_DATA_MAX_BATCH 65535
+int iaf_data_create(iaf_data_t** out, const unsigned char* images /* device, borrowed */, uint64_t n, size_t bytes_per_image,
+                    uint64_t seed, int deterministic);
+int iaf_data_destroy(iaf_data_t* d);
+int iaf_data_next_batch(iaf_data_t* d, unsigned char* out, long long* idx_out /* may be NULL */, int B, int rank, int world,
+                        int advance, void* stream);
+int iaf_data_seek(iaf_data_t* d, uint64_t step, void* stream);
+int iaf_data_skip(iaf_data_t* d, uint64_t steps, void* stream);
+int iaf_data_tell(iaf_data_t* d, uint64_t* step, void* stream);   /* synchronises; not during a capture */
+
 #ifdef __cplusplus
 }
 #endif
