@@ -89,6 +89,9 @@ SIGNATURES = {
     "iaf_lowerbound_stream_init": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, _vp]),
     "iaf_lowerbound_stream_update": (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int, ctypes.c_int, _vp]),
     "iaf_lowerbound_stream_finalize": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int, ctypes.c_int, _vp]),
+    "iaf_eval_reset": (ctypes.c_int, [_vp, _c_float_p, _c_float_p, ctypes.c_int, _vp]),
+    "iaf_eval_tail": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_size_t, ctypes.c_float, _c_float_p, ctypes.c_int, ctypes.c_int,
+                                     _c_float_p, _c_float_p, ctypes.c_int, _vp, _c_float_p, _c_float_p, _vp, _vp]),
     "iaf_stack_set_tuning": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5),
     "iaf_stack_set_precision": (ctypes.c_int, [_vp, ctypes.c_int]),
     "iaf_stack_get_precision": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4),

@@ -235,9 +235,7 @@ extern "C" int iaf_kl_combine(const float* logq0, const float* logdet, const flo
 __global__ __launch_bounds__(256) void iaf_colsum_kernel(const float* __restrict__ mat, float* __restrict__ out, int m, int n) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    float s = 0.f;
-    for (int i = 0; i < m; ++i) s += mat[(size_t)i * n + j];
-    out[j] = s;
+    out[j] = iaf_col_sum(mat, m, n, j);            // (iaf_kernels_misc.hpp: shared with iaf_eval_tail_kernel)
 }
 extern "C" int iaf_colsum(const float* mat, float* out, int m, int n, void* stream) {
     if (!mat || !out) return IAF_ERR_NULL;

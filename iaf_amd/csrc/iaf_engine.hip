@@ -2065,6 +2065,29 @@ extern "C" int iaf_lowerbound_stream_finalize(const float* run_max, const float*
     return (int)hipGetLastError();
 }
 
+// the tail of an evaluation pass and the epoch's record (iaf_kernels_misc.hpp: iaf_eval_tail_kernel): one workgroup per batch row
+static_assert(sizeof(EvalRec) == 32, "the evaluation record is 32 bytes (include/iaf_hip.h)");
+extern "C" int iaf_eval_reset(void* record, float* run_max, float* run_sum, int n, void* stream) {
+    if (!record || !run_max || !run_sum) return IAF_ERR_NULL;
+    if (n < 1 || n > 65535) return IAF_ERR_SHAPE;
+    if (((uintptr_t)record & 7) != 0) return IAF_ERR_WORKSPACE;
+    hipLaunchKernelGGL(iaf_eval_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (EvalRec*)record, run_max,
+                       run_sum, n);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_eval_tail(const float* x_out, const float* dec_log_stdv, const float* x, size_t n_per_row, float binsize,
+                             const float* layer_cost, int n_layers, int n, float* run_max, float* run_sum, int k,
+                             const long long* indices, float* per_image, float* bound, void* record, void* stream) {
+    if (!x_out || !dec_log_stdv || !x || !layer_cost || !run_max || !run_sum || !bound || !record) return IAF_ERR_NULL;
+    if (per_image && !indices) return IAF_ERR_NULL;
+    if (n < 1 || n > 65535 || n_layers < 1 || k < 1 || n_per_row == 0 || !(binsize > 0.f)) return IAF_ERR_SHAPE;
+    if (((uintptr_t)record & 7) != 0) return IAF_ERR_WORKSPACE;
+    hipLaunchKernelGGL(iaf_eval_tail_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, x_out, dec_log_stdv, x, n_per_row, binsize,
+                       layer_cost, n_layers, n, run_max, run_sum, k, indices, per_image, bound, (EvalRec*)record);
+    return (int)hipGetLastError();
+}
+
 extern "C" int iaf_compute_lowerbound(const float* log_pxz, const float* sum_kl, float* out, int n, int k, void* stream) {
     if (!log_pxz || !sum_kl || !out) return IAF_ERR_NULL;
     if (n <= 0 || k <= 0) return IAF_ERR_SHAPE;

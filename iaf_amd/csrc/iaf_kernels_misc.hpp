@@ -466,6 +466,15 @@ __global__ __launch_bounds__(256) void iaf_adamax_ema_guarded_kernel(float* __re
     }
 }
 
+// the pieces of the streaming log-sum-exp that iaf_eval_tail_kernel (below) shares with the three kernels here: the running sum
+// rescaled to the new maximum plus a chunk's sum, and the bound the state stands for after k weights (distributions.py:62)
+__device__ __forceinline__ float iaf_lb_rescaled_sum(float old_m, float old_s, float new_m, float s) {
+    return (old_m == -INFINITY ? 0.f : old_s * expf(old_m - new_m)) + s;
+}
+__device__ __forceinline__ float iaf_lb_bound(float run_max, float run_sum, int k) {
+    return -(-logf((float)k) + run_max + logf(run_sum));
+}
+
 // streaming logsumexp over k importance weights per image: one wave per image
 __global__ __launch_bounds__(256) void iaf_lb_update_kernel(float* run_max, float* run_sum, const float* log_pxz,
                                                            const float* sum_kl, int n, int kc) {
@@ -485,7 +494,7 @@ __global__ __launch_bounds__(256) void iaf_lb_update_kernel(float* run_max, floa
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) {
         const float old_s = run_sum[img];
-        run_sum[img] = (old_m == -INFINITY ? 0.f : old_s * expf(old_m - new_m)) + s;
+        run_sum[img] = iaf_lb_rescaled_sum(old_m, old_s, new_m, s);
         run_max[img] = new_m;
     }
 }
@@ -495,7 +504,7 @@ __global__ void iaf_lb_init_kernel(float* run_max, float* run_sum, int n) {
 }
 __global__ void iaf_lb_finalize_kernel(const float* run_max, const float* run_sum, float* out, int n, int k) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = -(-logf((float)k) + run_max[i] + logf(run_sum[i]));   // distributions.py:62
+    if (i < n) out[i] = iaf_lb_bound(run_max[i], run_sum[i], k);   // distributions.py:62
 }
 __global__ void iaf_lb_k1_kernel(const float* log_pxz, const float* sum_kl, float* out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -543,11 +552,10 @@ __global__ __launch_bounds__(256) void iaf_datainit_kernel(const float* x, const
 
 // discretized logistic log-likelihood, tf_utils/distributions.py:28-32 (call site tf_train.py:210): one workgroup per
 // batch row, out[b] = sum log(sigmoid(s + binsize/scale) - sigmoid(s) + 1e-7), s = (floor(x/binsize)*binsize - mean)/scale
-__global__ __launch_bounds__(256) void iaf_disc_logistic_kernel(const float* __restrict__ mean, const float* __restrict__ logscale,
-                                                               int scalar_scale, const float* __restrict__ sample,
-                                                               float* __restrict__ out, size_t n, float binsize) {
-    __shared__ float red[4];
-    const size_t base = (size_t)blockIdx.x * n;
+// (the row sum is a helper of its own: iaf_eval_tail_kernel below takes log_pxz from it too, bit for bit)
+__device__ __forceinline__ float iaf_disc_logistic_row(const float* __restrict__ mean, const float* __restrict__ logscale,
+                                                       int scalar_scale, const float* __restrict__ sample, size_t base, size_t n,
+                                                       float binsize, float* red) {
     float acc = 0.f;
     for (size_t i = threadIdx.x; i < n; i += 256) {
         const float scale = expf(scalar_scale ? logscale[0] : logscale[base + i]);
@@ -564,7 +572,98 @@ __global__ __launch_bounds__(256) void iaf_disc_logistic_kernel(const float* __r
         }
         acc += logf(diff + 1e-7f);
     }
-    const float tot = block_sum_256(acc, red);
+    return block_sum_256(acc, red);
+}
+__global__ __launch_bounds__(256) void iaf_disc_logistic_kernel(const float* __restrict__ mean, const float* __restrict__ logscale,
+                                                               int scalar_scale, const float* __restrict__ sample,
+                                                               float* __restrict__ out, size_t n, float binsize) {
+    __shared__ float red[4];
+    const float tot = iaf_disc_logistic_row(mean, logscale, scalar_scale, sample, (size_t)blockIdx.x * n, n, binsize, red);
     if (threadIdx.x == 0) out[blockIdx.x] = tot;
+}
+
+// out[j] of iaf_colsum_kernel (csrc/iaf_conv3x3_host.hpp): ((0 + mat[0][j]) + mat[1][j]) + ..., row order
+__device__ __forceinline__ float iaf_col_sum(const float* __restrict__ mat, int m, int n, int j) {
+    float s = 0.f;
+    for (int i = 0; i < m; ++i) s += mat[(size_t)i * n + j];
+    return s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The tail of one evaluation pass (tf_train.py:210, 198-200, 218 and run_eval's accumulation, :313-325) as ONE launch: what
+// iaf_disc_logistic_kernel, iaf_colsum_kernel, iaf_lb_update_kernel (kc = 1), iaf_lb_finalize_kernel and a sum over the batch do,
+// with the same helpers in the same order -- one workgroup per batch row.  The record counts the passes of the current batch, so a
+// replayed graph needs no host to say which pass closes the batch; the last workgroup to arrive (an agent-scope counter, as in
+// iaf_guard_sumsq_scan_kernel above) adds the closed batch to the epoch's sums and moves the pass counter.  Only thread 0 of a
+// workgroup reads the counter, before it arrives: the last workgroup's write cannot race a read of the same launch.
+// ---------------------------------------------------------------------------------------------
+struct EvalRec { double loss_sum; unsigned long long images, nonfinite; unsigned pass, arrivals; };
+__global__ __launch_bounds__(256) void iaf_eval_tail_kernel(const float* __restrict__ x_out, const float* __restrict__ dec_log_stdv,
+                                                           const float* __restrict__ x, size_t n_per_row, float binsize,
+                                                           const float* __restrict__ layer_cost, int n_layers, int n, float* run_max,
+                                                           float* run_sum, int k, const long long* __restrict__ indices,
+                                                           float* per_image, float* bound, EvalRec* rec) {
+    __shared__ float red[4];
+    __shared__ double red64[4];
+    __shared__ unsigned s_pass, s_last;
+    const int b = blockIdx.x;
+    unsigned p = 0u;
+    float kl = 0.f;
+    if (threadIdx.x == 0) {
+        p = __hip_atomic_load(&rec->pass, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_pass = p;
+        kl = iaf_col_sum(layer_cost, n_layers, n, b);
+    }
+    const float log_pxz = iaf_disc_logistic_row(x_out, dec_log_stdv, 1, x, (size_t)b * n_per_row, n_per_row, binsize, red);
+    if (threadIdx.x == 0) {
+        const bool closing = p + 1u >= (unsigned)k;
+        const float w = log_pxz - kl;
+        const float old_m = run_max[b], old_s = run_sum[b];
+        const float new_m = fmaxf(old_m, fmaxf(-INFINITY, w));                        // iaf_lb_update_kernel, one weight
+        float s = 0.f;
+        s += expf(w - new_m);
+        float rs = iaf_lb_rescaled_sum(old_m, old_s, new_m, s), rm = new_m;
+        if (closing) {
+            const float bd = iaf_lb_bound(rm, rs, k);
+            // (agent scope: the workgroup that sums the bounds may sit on another XCD)
+            __hip_atomic_store((unsigned*)bound + b, __float_as_uint(bd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (per_image) per_image[indices[b]] = bd;
+            rm = -INFINITY; rs = 0.f;                                                  // armed for the next batch
+        }
+        run_max[b] = rm;
+        run_sum[b] = rs;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                               // the bound is in memory before this workgroup arrives
+        s_last = __hip_atomic_fetch_add(&rec->arrivals, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    const unsigned pass = s_pass;
+    const bool closing = pass + 1u >= (unsigned)k;
+    if (closing) {
+        // fixed order: thread t adds rows t, t + 256, ... in index order, then the shuffle / LDS tree; no float atomics
+        double sum = 0.0, bad = 0.0;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const float v = __uint_as_float(__hip_atomic_load((unsigned*)bound + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            sum += (double)v;
+            bad += iaf_nonfinite(v) ? 1.0 : 0.0;                                       // (a count below 2^53: exact)
+        }
+        sum = iaf_block_sum_f64(sum, red64);
+        bad = iaf_block_sum_f64(bad, red64);
+        if (threadIdx.x == 0) {
+            rec->loss_sum += sum;
+            rec->images += (unsigned long long)n;
+            rec->nonfinite += (unsigned long long)bad;
+        }
+    }
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&rec->pass, closing ? 0u : pass + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&rec->arrivals, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// zeroes the record and arms the streaming state of n rows
+__global__ __launch_bounds__(256) void iaf_eval_reset_kernel(EvalRec* rec, float* run_max, float* run_sum, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { run_max[i] = -INFINITY; run_sum[i] = 0.f; }
+    if (i == 0) { rec->loss_sum = 0.0; rec->images = 0ull; rec->nonfinite = 0ull; rec->pass = 0u; rec->arrivals = 0u; }
 }
 

@@ -27,10 +27,10 @@ class IAFPosterior(object):
     def set_up_state(self, qz_mean, qz_logsd, up_context):
         self.qz_mean, self.qz_logsd, self.up_context = qz_mean, qz_logsd, up_context
 
-    def down(self, pz_mean, pz_logsd, rz_mean, rz_logsd, down_context, eps, want_kl_elem=False):
-        """Returns dict(z, kl_obj, kl_cost): the values tf_train.py:85-87 hand to the rest of down()."""
+    def down(self, pz_mean, pz_logsd, rz_mean, rz_logsd, down_context, eps, want_kl_elem=False, out=None):
+        """Returns dict(z, kl_obj, kl_cost): the values tf_train.py:85-87 hand to the rest of down().  out: ARStack.posterior_block's."""
         return self.stack.posterior_block(self.qz_mean, self.qz_logsd, rz_mean, rz_logsd, pz_mean, pz_logsd,
-                                          self.up_context, down_context, eps, self.kl_min, want_kl_elem)
+                                          self.up_context, down_context, eps, self.kl_min, want_kl_elem, out=out)
 
 
 def gaussian_sample(mean, logsd, eps):
@@ -139,8 +139,8 @@ class IAFLayer(object):
     def up(self, inp, autotune=False):
         return self._range_retry(self._up, inp, autotune)
 
-    def down(self, inp, eps, autotune=False, eps_prior=None):
-        return self._range_retry(self._down, inp, eps, autotune, eps_prior)
+    def down(self, inp, eps, autotune=False, eps_prior=None, kl_cost_out=None):
+        return self._range_retry(self._down, inp, eps, autotune, eps_prior, kl_cost_out)
 
     def generate_down(self, inp, eps_prior):
         """down() of mode "sample" (tf_train.py:46-66, 87-95) without the up pass: z = the prior sample, no IAF step, no KL.  inp
@@ -170,16 +170,19 @@ class IAFLayer(object):
         self.posterior.set_up_state(qz_mean, qz_logsd, up_context)                                        # :38
         return self.up_conv3(h, elu_input=True, residual=inp, autotune=autotune)[0]                       # :40-44
 
-    def _down(self, inp, eps, autotune=False, eps_prior=None):
+    def _down(self, inp, eps, autotune=False, eps_prior=None, kl_cost_out=None):
         """Returns (output, kl_obj, kl_cost) like tf_train.py:95.  `eps` is the posterior noise (mode "train"),
         `eps_prior` the prior noise modes "init" / "sample" draw instead (tf_train.py:60-61).  autotune=True: the first
-        call at a new (B,H,W) searches the launch shapes of the plain convs (cuDNN's algorithm search in the reference)."""
+        call at a new (B,H,W) searches the launch shapes of the plain convs (cuDNN's algorithm search in the reference).
+        kl_cost_out (mode "train"): a contiguous fp32 [B] tensor the posterior block writes kl_cost into, e.g. a row of a
+        [layers, B] matrix; the returned kl_cost is then that tensor."""
         zs, hs = self.z_size, self.h_size
         pz_mean, pz_logsd, rz_mean, rz_logsd, down_context, h_det = self.down_conv1(
             inp, elu_input=True, split=[zs] * 4 + [hs] * 2, autotune=autotune)                            # :52-54
         po = self.posterior
         if self.mode == "train":
-            blk = po.down(pz_mean, pz_logsd, rz_mean, rz_logsd, down_context, eps)                        # :56-85
+            blk = po.down(pz_mean, pz_logsd, rz_mean, rz_logsd, down_context, eps,
+                          out=None if kl_cost_out is None else dict(kl_cost=kl_cost_out))                 # :56-85
         else:
             if eps_prior is None:
                 raise ValueError("modes 'init' and 'sample' sample the PRIOR (tf_train.py:60-61): pass eps_prior")

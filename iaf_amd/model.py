@@ -92,16 +92,25 @@ class CVAE1(object):
             order = [(i, j) for i in range(self.depth) for j in range(self.num_blocks)]
             convs = [(ij, nm) for ij in order
                      for nm in ("up_conv1", "up_conv3", "down_conv1") + (() if self.layers[ij[0]][ij[1]].downsample else ("down_conv2",))]
-            self._prep = dict(order=order, convs=convs, s=PrepBatch([self.layers[i][j].posterior.stack for i, j in order]),
-                              c=ConvPrepBatch([getattr(self.layers[ij[0]][ij[1]], nm) for ij, nm in convs]))
+            try:
+                self._prep = dict(order=order, convs=convs, s=PrepBatch([self.layers[i][j].posterior.stack for i, j in order]),
+                                  c=ConvPrepBatch([getattr(self.layers[ij[0]][ij[1]], nm) for ij, nm in convs]))
+            except _capi.UnsupportedError:
+                # channel counts the batched prep launches do not cover (the generic stacks): every object's own prep launch, as load()
+                # runs them -- each re-derives its weights when a variable's (pointer, version) has changed since its last prep
+                self._prep = dict(order=order, per_object=True)
         P = self._prep
-        P["s"].run([IAFLayer.stack_params(self._lparams[ij]) for ij in P["order"]])
-        P["c"].run([(self._lparams[ij][nm + "/V"], self._lparams[ij][nm + "/g"], self._lparams[ij][nm + "/b"]) for ij, nm in P["convs"]])
-        for i, j in P["order"]:
-            layer = self.layers[i][j]
-            if layer.downsample:
-                lp = self._lparams[(i, j)]
-                layer.down_conv2.prepare_deconv(lp["down_deconv2/V"], lp["down_deconv2/g"], lp["down_deconv2/b"], force=True)
+        if P.get("per_object"):
+            for i, j in P["order"]:
+                self.layers[i][j].load(self._lparams[(i, j)])
+        else:
+            P["s"].run([IAFLayer.stack_params(self._lparams[ij]) for ij in P["order"]])
+            P["c"].run([(self._lparams[ij][nm + "/V"], self._lparams[ij][nm + "/g"], self._lparams[ij][nm + "/b"]) for ij, nm in P["convs"]])
+            for i, j in P["order"]:
+                layer = self.layers[i][j]
+                if layer.downsample:
+                    lp = self._lparams[(i, j)]
+                    layer.down_conv2.prepare_deconv(lp["down_deconv2/V"], lp["down_deconv2/g"], lp["down_deconv2/b"], force=True)
         _capi.check(lib.iaf_convk_weightnorm(_ptr(p["x_enc/V"]), _ptr(p["x_enc/g"]), _ptr(self._w_enc), 5, 5, 3, hs, 0, _stream()))
         _capi.check(lib.iaf_convk_weightnorm(_ptr(p["x_dec/V"]), _ptr(p["x_dec/g"]), _ptr(self._w_dec), 5, 5, hs, 3, 1, _stream()))
 
@@ -400,7 +409,10 @@ class CVAE1(object):
         return xf
 
     def _top_down(self, xf, B, noise, terms=False):
-        """tf_train.py:189-218 on the state _bottom_up left: h_top, the down pass, x_dec, the likelihood, obj and loss"""
+        """tf_train.py:189-218 on the state _bottom_up left: h_top, the down pass, x_dec, the likelihood, obj and loss.
+        terms=True: (log_pxz [n], kl_cost [n]) instead.  terms="raw": the pass stops behind x_dec and returns what the likelihood and the
+        bound are made of -- (x_out, xf, layer_cost [nl, n]: every layer's kl_cost, top-down, written by the layers into the rows of one
+        matrix) -- with no discretized_logistic, iaf_colsum or lower-bound launch and no gathering copy (EvalPass: iaf_eval_tail)."""
         lib, p, hs, k = _capi.lib(), self.params, self.h_size, self.k
         n, S, dev = int(xf.shape[0]), int(xf.shape[2]), xf.device
         St = S // 2 ** self.depth
@@ -408,14 +420,26 @@ class CVAE1(object):
         _capi.check(lib.iaf_tile_channels(_ptr(p["h_top"]), _ptr(h), n, hs, St * St, _stream()))           # :189-192
         nl = self.depth * self.num_blocks
         objs, costs = [], []
+        raw = isinstance(terms, str) and terms == "raw"
+        cost_rows = torch.empty((nl, n), dtype=torch.float32, device=dev) if raw else None
         li = 0
         for level in reversed(self.layers):                                                                # :195-200
             for layer in reversed(level):
                 eps_prior, eps_post = noise[2 * li], noise[2 * li + 1]
-                h, cur_obj, cur_cost = layer.down(h, eps_post, eps_prior=eps_prior)
+                if raw:
+                    h, cur_obj, cur_cost = layer.down(h, eps_post, eps_prior=eps_prior, kl_cost_out=cost_rows[li])
+                    if cur_cost.data_ptr() != cost_rows[li].data_ptr():       # (a mode whose down() has no posterior block to write it)
+                        cost_rows[li].copy_(cur_cost)
+                else:
+                    h, cur_obj, cur_cost = layer.down(h, eps_post, eps_prior=eps_prior)
                 objs.append(cur_obj)
                 costs.append(cur_cost)
                 li += 1
+        if raw:
+            x_out = torch.empty((n, 3, S, S), dtype=torch.float32, device=dev)
+            _capi.check(lib.iaf_deconvk_forward(_ptr(h), _ptr(self._w_dec), _ptr(p["x_dec/b"]), _ptr(x_out), n, hs, S // 2, S // 2, 3, 5, 5,
+                                                2, 1, -0.5 + 1 / 512., 0.5 - 1 / 512., _stream()))         # :206-208
+            return x_out, xf, cost_rows
         objs, costs = torch.stack(objs), torch.stack(costs)          # [nl, n] (one gathering copy each; the sums are iaf_colsum's)
         kl_obj = torch.empty(n, dtype=torch.float32, device=dev)
         kl_cost = torch.empty(n, dtype=torch.float32, device=dev)

@@ -76,13 +76,14 @@ class FlatParams(object):
         self.slot_m = torch.zeros_like(self.params)
         self.slot_v = torch.zeros_like(self.params)
         self.ema = torch.empty_like(self.params)
-        self.p, self.g = {}, {}
+        self.p, self.g, self.e = {}, {}, {}        # (e: the EMA under the same names -- CVAE1.load(flat.e) evaluates the averaged weights)
         off = 0
         for k, t in items:
             n = t.numel()
             self.p[k] = self.params[off:off + n].view(t.shape)
             self.p[k].copy_(t)
             self.g[k] = self.grads[off:off + n].view(t.shape)
+            self.e[k] = self.ema[off:off + n].view(t.shape)
             off += ((n + 3) // 4) * 4
         self.ema.copy_(self.params)
 

@@ -524,3 +524,9 @@ class TrainStep(object):
     def graphed(self):
         """True if the steps replay a captured hipGraph"""
         return self._graph is not None
+
+    def ema_params(self):
+        """the EMA of the variables (tf_train.py:157-158) as name -> view into ts.flat.ema, the names and shapes of model.params: load a
+        second CVAE1 of the same geometry from it ONCE (eval_model.load(ts.ema_params()); the reference's Saver(model.avg_dict),
+        tf_train.py:297) and every later EvalPass.run() evaluates the average as it stands, without a copy"""
+        return self.flat.e

@@ -344,6 +344,27 @@ int iaf_kl_combine(const float* logq0, const float* logdet, const float* logp, f
 int iaf_colsum(const float* mat, float* out, int m, int n, void* stream);
 int iaf_lowerbound_stream_finalize(const float* run_max, const float* run_sum, float* out, int n, int k_total,
                                    void* stream);
+/* The tail of one evaluation pass (tf_train.py:210, 198-200, 218; run_eval's sums, :313-325) in ONE launch, and the device record
+ * an epoch accumulates in -- so that a replayed hipGraph evaluates batch after batch, k passes each, with no host code between.
+ *   record: 32 bytes of device memory, 8-byte aligned (else IAF_ERR_WORKSPACE):
+ *           double loss_sum; uint64 images; uint64 nonfinite; uint32 pass; uint32 arrivals
+ * iaf_eval_reset zeroes the record and arms the streaming state of n rows (run_max = -inf, run_sum = 0).
+ * iaf_eval_tail: one workgroup per batch row b < n (1 <= n <= 65535):
+ *   log_pxz[b] = the row sum of iaf_discretized_logistic(x_out, dec_log_stdv (scalar), x) over n_per_row elements;
+ *   kl[b]      = iaf_colsum of layer_cost [n_layers, n];
+ *   (run_max[b], run_sum[b]) take the weight log_pxz[b] - kl[b] as iaf_lowerbound_stream_update does at k_chunk = 1
+ *   -- each of them bit for bit what those entry points give.  p = record.pass counts the passes of the current batch:
+ *   p + 1 <  k: nothing more, and the last workgroup to arrive sets pass = p + 1;
+ *   p + 1 >= k: the closing pass.  bound[b] = iaf_lowerbound_stream_finalize's value for k (k = 1: kl[b] - log_pxz[b] exactly);
+ *               per_image[indices[b]] = bound[b] when per_image is not NULL (indices: the int64 [n] vector iaf_data_next_batch
+ *               writes; it may be NULL only together with per_image; the caller vouches for its range); the row's state is armed
+ *               again; the last workgroup to arrive adds the fp64 sum of bound[0..n) to loss_sum (a fixed order, no float
+ *               atomics: the same bits on every run), n to images, the number of non-finite bounds to nonfinite, and sets pass = 0.
+ * Errors: NULL pointers IAF_ERR_NULL; n, n_layers, k < 1, n > 65535, n_per_row == 0 or binsize <= 0 IAF_ERR_SHAPE.  Capturable. */
+int iaf_eval_reset(void* record, float* run_max, float* run_sum, int n, void* stream);
+int iaf_eval_tail(const float* x_out, const float* dec_log_stdv, const float* x, size_t n_per_row, float binsize,
+                  const float* layer_cost, int n_layers, int n, float* run_max, float* run_sum, int k, const long long* indices,
+                  float* per_image, float* bound, void* record, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Tuning / introspection (not part of the reference surface)
