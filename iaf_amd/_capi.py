@@ -31,6 +31,13 @@ IAF_VARIANT_THEANO_FLIPMASK = 2
 
 _c_float_p = ctypes.c_void_p      # device pointers travel as integers (tensor.data_ptr())
 _vp = ctypes.c_void_p
+IAF_STATE_MAX_PARTS = 8
+
+
+class StatePart(ctypes.Structure):
+    """iaf_state_part_t: one part of iaf_state_snapshot (dst may be None)"""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bytes", ctypes.c_size_t)]
+
 
 # name -> (restype, argtypes); must list every symbol include/iaf_hip.h declares
 SIGNATURES = {
@@ -211,6 +218,10 @@ SIGNATURES = {
     "iaf_data_seek": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
     "iaf_data_skip": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp]),
     "iaf_data_tell": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), _vp]),
+    "iaf_state_snapshot": (ctypes.c_int, [ctypes.POINTER(StatePart), ctypes.c_int, _vp, _vp]),
+    "iaf_rng_step_ptr": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "iaf_data_step_ptr": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "iaf_skip_counter_ptr": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "iaf_conv3x3_work": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 2),
 }
 

@@ -3013,6 +3013,49 @@ extern "C" int iaf_data_tell(iaf_data_t* d, uint64_t* step, void* stream) {
     return IAF_OK;
 }
 
+// the state snapshot (iaf_kernels_data.hpp): a memset of the digests and ONE launch; the table travels in the kernel arguments.  The three
+// getters hand out the device's view of counters their objects already own, so that a snapshot can take them in the same launch.
+extern "C" int iaf_state_snapshot(const iaf_state_part_t* parts, int n_parts, uint64_t* digests, void* stream) {
+    if (!parts || !digests) return IAF_ERR_NULL;
+    if (n_parts < 1 || n_parts > IAF_STATE_MAX_PARTS) return IAF_ERR_SHAPE;
+    IafStateTable T;
+    memset(&T, 0, sizeof(T));
+    for (int i = 0; i < n_parts; ++i) {
+        if (!parts[i].src) return IAF_ERR_NULL;
+        if (parts[i].bytes == 0 || (parts[i].bytes & 3) != 0) return IAF_ERR_SHAPE;
+        if ((((uintptr_t)parts[i].src | (uintptr_t)parts[i].dst) & 3) != 0) return IAF_ERR_WORKSPACE;
+        T.src[i] = (const unsigned*)parts[i].src;
+        T.dst[i] = (unsigned*)parts[i].dst;
+        T.words[i] = (unsigned long long)parts[i].bytes / 4;
+    }
+    if (((uintptr_t)digests & 7) != 0) return IAF_ERR_WORKSPACE;
+    T.n = n_parts;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(digests, 0, sizeof(uint64_t) * (size_t)n_parts, st);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = iaf_state_assign(T, IAF_STATE_MAX_BLOCKS);      // (the chip's share of workgroups, in proportion to the parts' sizes)
+    hipLaunchKernelGGL(iaf_state_snapshot_kernel, dim3(grid), dim3(IAF_STATE_THREADS), 0, st, T, (unsigned long long*)digests);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_rng_step_ptr(iaf_rng_t* r, const uint64_t** step) {
+    if (!r || !step) return IAF_ERR_NULL;
+    *step = (const uint64_t*)r->d_step;
+    return IAF_OK;
+}
+
+extern "C" int iaf_data_step_ptr(iaf_data_t* d, const uint64_t** step) {
+    if (!d || !step) return IAF_ERR_NULL;
+    *step = (const uint64_t*)d->d_step;
+    return IAF_OK;
+}
+
+extern "C" int iaf_skip_counter_ptr(const iaf_skip_counter_t* c, const unsigned** count) {
+    if (!c || !count) return IAF_ERR_NULL;
+    *count = c->dev;
+    return IAF_OK;
+}
+
 extern "C" int iaf_layer_work(const iaf_stack_t* s, int layer, int B, int H, int W, double* live_flops,
                               double* dense_flops, double* bytes) {
     if (!s) return IAF_ERR_NULL;

@@ -187,6 +187,8 @@ class TrainStep(object):
             self._guard = torch.zeros(4, dtype=torch.int32, device=dev)
             self._skips = _SkipCounter()
         self._host_skips = 0
+        self.steps = 0                    # __call__s so far (a restore sets it to the saved run's)
+        self._skip_base = 0               # what a restore adds to the skip counter: the saved run's skips
         self._acted = 0                   # the count at the last recovery
         self._aborted = False             # an eager step could not finish on this rank (an object switched kernels in the middle)
         self._seen = set()                # range objects already moved to bf16 planes
@@ -414,6 +416,11 @@ class TrainStep(object):
         return self._xb
 
     def __call__(self, x=None, noise=None):
+        obj = self._step(x, noise)
+        self.steps += 1
+        return obj
+
+    def _step(self, x, noise):
         src, data = self.noise_source, self.data
         if x is None and data is None:
             raise ValueError("TrainStep: pass the step's batch, or build the step with data=")
@@ -463,10 +470,45 @@ class TrainStep(object):
 
     @property
     def skipped(self):
-        """the number of updates skipped so far (synchronises the device)"""
+        """the number of updates skipped so far (synchronises the device); after a restore, the saved run's count plus this step's own"""
         if self.on_device:
             torch.cuda.synchronize()
-        return self._count()
+        return self._skip_base + self._count()
+
+    @property
+    def global_step(self):
+        """steps - skipped: the updates applied so far, the reference's global_step (synchronises the device)"""
+        return self.steps - self.skipped
+
+    # -- checkpoints (iaf_amd/checkpoint.py) ---------------------------------------------------------------------------------------------
+    def snapshot(self, into=None):
+        """snap = ts.snapshot(): ONE launch on the current stream (iaf_state_snapshot) copies ts.flat's variables, slots and EMA into
+        staging buffers the Snapshot owns, the noise source's and the dataset's step and the skip count into its header tensor, and leaves
+        a digest of each; an event follows.  Reads only, does not synchronise, copies nothing to the host; not while the current stream
+        captures (RuntimeError).  into=: an earlier Snapshot of the same size, reused.  Host replicas: tensor clones, the numpy digest.
+        snap.save(path) writes the file."""
+        from . import checkpoint
+        return checkpoint.take_snapshot(self, into)
+
+    def restore(self, ck_or_path):
+        """Continue the run a checkpoint was saved from (a Checkpoint or a path), before the first step or between two steps: the
+        variables' names, shapes and order, world, towers and -- with a dataset -- batch_size and the dataset's size must be this step's
+        (ValueError names the first difference); lr, betas, eps and ema_decay stay this step's.  The arrays are checked by their digests
+        ON THE DEVICE before ts.flat is touched (IafHipError), then copied into ts.flat in place; the noise source and the dataset are
+        sought to the saved steps; ts.steps and ts.skipped continue the saved counts; the stacks and convs the saved run had moved to bf16
+        planes are moved here.  The summaries record starts as after summaries(reset=True).  Synchronises."""
+        from . import checkpoint
+        return checkpoint.restore(self, ck_or_path)
+
+    def _reset_record(self):
+        """the summaries record as after summaries(reset=True) (nothing to do before the first step has made one)"""
+        if not self.with_summaries or self._rec is None:
+            return
+        if self.on_device:
+            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _capi.check(_capi.lib().iaf_train_summaries_reset(ctypes.c_void_p(self._rec.data_ptr()), self._geom[0], st))
+        else:
+            self._rec.update(acc=torch.zeros_like(self._rec["acc"]), last=torch.zeros_like(self._rec["last"]), steps=0, skipped=0)
 
     # -- summaries ------------------------------------------------------------------------------------------------------------------
     def _read_record(self):
@@ -504,11 +546,7 @@ class TrainStep(object):
         acc, _, steps, skipped = rec
         mean = acc / steps if steps else acc * float("nan")
         if reset:
-            if self.on_device:
-                st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                _capi.check(_capi.lib().iaf_train_summaries_reset(ctypes.c_void_p(self._rec.data_ptr()), self._geom[0], st))
-            else:
-                self._rec.update(acc=torch.zeros_like(self._rec["acc"]), last=torch.zeros_like(self._rec["last"]), steps=0, skipped=0)
+            self._reset_record()
         return self._as_dict(mean, steps, skipped)
 
     def last_summaries(self):

@@ -857,6 +857,37 @@ int iaf_data_seek(iaf_data_t* d, uint64_t step, void* stream);
 int iaf_data_skip(iaf_data_t* d, uint64_t steps, void* stream);
 int iaf_data_tell(iaf_data_t* d, uint64_t* step, void* stream);   /* synchronises; not during a capture */
 
+/* ------------------------------------------------------------------------------------------
+ * The state snapshot: a consistent copy of a training run's state, taken on the stream between two steps without stopping the run
+ * (the reference's saver.save, tf_train.py:286-287; iaf_amd/checkpoint.py builds the file around it).
+ *
+ * iaf_state_snapshot: a memset of digests[0..n_parts) and ONE launch.  For every part (1 <= n_parts <= 8) the launch reads `src` once,
+ *   writes the same bytes to `dst` when dst is not NULL, and leaves digests[p] (device memory, 8-byte aligned), the 64-bit digest of the
+ *   part's 32-bit words w_0 .. w_{n-1} (little endian, n = bytes / 4):
+ *       k_i = ((2 i + 1) * 0x9E3779B1) mod 2^32;     digest = sum_i (w_i + 1) * k_i  mod 2^64,   (w_i + 1) taken as a 64-bit value.
+ *   A sum mod 2^64: independent of reduction order and grid size, bit-equal to a restatement in integers (tests/state_reference.py).  It
+ *   guards against truncation (every word counts, a zero word too), torn writes and stray bytes.  It is NOT a cryptographic hash: anyone
+ *   who wants a collision can make one.
+ *   Known answers:  no words -> 0 (by definition; the call itself refuses an empty part);   one zero word -> 0x9e3779b1;
+ *       words 0,1,2,3,4 -> 0x6b69628af;     five words 0xFFFFFFFF -> 0x736ae24900000000.
+ *   The table is read during the call and travels in the kernel arguments: no upload and no host pointer the launch reads later, so the
+ *   call can be captured, and a replay leaves the digest of what THAT replay read (the memset is part of the capture).
+ *   src, dst: any 4-byte alignment.  16-byte loads per lane over the body behind a scalar head up to src's first 16-byte boundary;
+ *   16-byte stores where dst is congruent to src mod 16, dword stores where it is not.  src and dst of one call must not overlap, and
+ *   nothing else may write a part while the launch runs (stream order does that for state the same stream updates).
+ *   Errors, before any device work: IAF_ERR_NULL (table, digests, a src); IAF_ERR_SHAPE (n_parts outside 1..8, bytes 0 or not a multiple
+ *   of 4); IAF_ERR_WORKSPACE (a pointer not 4-byte aligned, digests not 8-byte aligned).
+ * iaf_rng_step_ptr / iaf_data_step_ptr / iaf_skip_counter_ptr: the counter the object already owns, as the DEVICE sees it (the noise
+ *   source's and the dataset's 64-bit step in device memory; the skip counter's mapped word) -- for a snapshot part.  Nothing moves; the
+ *   pointer lives as long as the object and is for reading.
+ * ------------------------------------------------------------------------------------------ */
+#define IAF_STATE_MAX_PARTS 8
+typedef struct { const void* src; void* dst; size_t bytes; } iaf_state_part_t;   /* bytes % 4 == 0, bytes >= 4; dst may be NULL */
+int iaf_state_snapshot(const iaf_state_part_t* parts, int n_parts /* 1..8 */, uint64_t* digests /* device, n_parts */, void* stream);
+int iaf_rng_step_ptr(iaf_rng_t* r, const uint64_t** step);
+int iaf_data_step_ptr(iaf_data_t* d, const uint64_t** step);
+int iaf_skip_counter_ptr(const iaf_skip_counter_t* c, const unsigned** count);
+
 #ifdef __cplusplus
 }
 #endif
