@@ -4,6 +4,8 @@ fails, this module raises."""
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IAF_HIP_LIB") or os.path.join(_HERE, "_lib", "libiaf_hip.so")   # env override: dev experiments
 
@@ -277,7 +279,6 @@ def destroy(name, handle):
     stream capture runs invalidates that capture (torch.cuda.graph captures in global mode and no longer collects garbage before
     it begins, so Python's cyclic GC may finalise an engine object in the middle of one).  During a capture on the current stream
     the call is put off; the first destroy() outside a capture makes the calls put off before its own, in their order."""
-    import torch
     if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():
         _deferred.append((name, handle))
         return
@@ -285,6 +286,81 @@ def destroy(name, handle):
         n, h = _deferred.pop(0)
         getattr(lib(), n)(h)
     getattr(lib(), name)(handle)
+
+
+class Handle(object):
+    """The owner of one native handle: made by the library's `create` (the handle comes back through its first argument, `args`
+    follow), destroyed ONCE, by close() or the finaliser, through destroy() and the family's *_destroy.  `h` is the handle as the
+    ctypes.c_void_p the library's calls take (an object keeps it as obj._h); nothing is destroyed when `create` failed."""
+
+    def __init__(self, create, *args):
+        self.h, self._destroy = ctypes.c_void_p(), None
+        check(getattr(lib(), create)(ctypes.byref(self.h), *args))
+        self._destroy = create[:create.index("_create")] + "_destroy"
+
+    def close(self):
+        name, self._destroy = getattr(self, "_destroy", None), None
+        if name and self.h:
+            destroy(name, self.h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ptr(t):
+    """the device address of a tensor as the library takes it (None: a null pointer)"""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def stream():
+    """the current stream as the library takes it"""
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def int_in(v, lo, hi=None):
+    """True for an int (no bool) with lo <= v < hi (hi=None: no upper end)"""
+    return not isinstance(v, bool) and isinstance(v, int) and lo <= v and (hi is None or v < hi)
+
+
+def counter_address(getter, handle):
+    """the device address one of the *_ptr getters hands out for a counter its object owns"""
+    p = ctypes.c_void_p()
+    check(getattr(lib(), getter)(handle, ctypes.byref(p)))
+    return p.value
+
+
+class StepCounter(object):
+    """The 64-bit step counter in device memory behind self._h, for the family of entry points named by `_prefix` (iaf_rng, iaf_data):
+    a launch of the owner reads it and, when it advances, a one-thread launch behind it adds one."""
+    _prefix = None
+
+    def _step_call(self, op, *args):
+        check(getattr(lib(), "%s_%s" % (self._prefix, op))(self._h, *args))
+
+    def seek(self, step):
+        """set the step counter (enqueued on the current stream)"""
+        if not int_in(step, 0, 1 << 64):
+            raise ValueError("step must be an int in [0, 2**64), got %r" % (step,))
+        self._step_call("seek", step, stream())
+
+    def skip(self, steps=1):
+        """add `steps` to the step counter (enqueued on the current stream)"""
+        if not int_in(steps, 0, 1 << 64):
+            raise ValueError("steps must be an int in [0, 2**64), got %r" % (steps,))
+        self._step_call("skip", steps, stream())
+
+    def tell(self):
+        """the step the next launch on the current stream will read (synchronises that stream; not during a capture)"""
+        v = ctypes.c_uint64()
+        self._step_call("tell", ctypes.byref(v), stream())
+        return int(v.value)
+
+    def counter_ptr(self):
+        """the counter's device address (what a state snapshot copies)"""
+        return counter_address(self._prefix + "_step_ptr", self._h)
 
 
 def error_string(code):

@@ -23,14 +23,13 @@ restores every rank.
 
 The summaries record of TrainStep(summaries=True) is not part of a checkpoint: a restored step starts its record as it does after
 summaries(reset=True)."""
-import ctypes
 import json
 import os
 
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _recover
 
 MAGIC = b"IAFCKPT1"
 VERSION = 1
@@ -78,20 +77,10 @@ def _views(arr, layout):
     return out
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _counter_ptr(fn, handle):
-    p = ctypes.c_void_p()
-    _capi.check(getattr(_capi.lib(), fn)(handle, ctypes.byref(p)))
-    return p.value
-
-
 def _launch(parts, digests):
     """iaf_state_snapshot on the current stream; parts: (src pointer, dst pointer or None, bytes)"""
     table = (_capi.StatePart * len(parts))(*[_capi.StatePart(s, d, n) for s, d, n in parts])
-    _capi.check(_capi.lib().iaf_state_snapshot(table, len(parts), ctypes.c_void_p(digests.data_ptr()), _stream()))
+    _capi.check(_capi.lib().iaf_state_snapshot(table, len(parts), _capi.ptr(digests), _capi.stream()))
     torch.autograd.graph.increment_version(digests)
 
 
@@ -130,10 +119,10 @@ class Snapshot(object):
         parts = [(s.data_ptr(), b.data_ptr(), nb) for s, b in zip(srcs, self.bufs)]
         hp = self.header.data_ptr()
         if ts.noise_source is not None:
-            parts.append((_counter_ptr("iaf_rng_step_ptr", ts.noise_source._h), hp + 4 * _H_NOISE, 8))
+            parts.append((ts.noise_source.counter_ptr(), hp + 4 * _H_NOISE, 8))
         if ts.data is not None:
-            parts.append((_counter_ptr("iaf_data_step_ptr", ts.data._h), hp + 4 * _H_DATA, 8))
-        parts.append((_counter_ptr("iaf_skip_counter_ptr", ts._skips._h), hp + 4 * _H_SKIP, 4))
+            parts.append((ts.data.counter_ptr(), hp + 4 * _H_DATA, 8))
+        parts.append((ts._skips.counter_ptr(), hp + 4 * _H_SKIP, 4))
         _launch(parts, self.digests)
         torch.autograd.graph.increment_version(tuple(self.bufs) + (self.header,))
         self.event = torch.cuda.Event()
@@ -178,7 +167,7 @@ class Snapshot(object):
         m["global_step"] = m["steps"] - m["skipped"]
         m["noise_step"] = int(words[_H_NOISE]) | int(words[_H_NOISE + 1]) << 32 if self._has[0] else None
         m["data_step"] = int(words[_H_DATA]) | int(words[_H_DATA + 1]) << 32 if self._has[1] else None
-        moved = set(ts._seen) | {i for i, o in enumerate(ts._objects) if o.range_errors()}
+        moved = ts._seen | _recover.flagged(ts._objects)
         m["moved"] = sorted(int(i) for i in moved)
         m["range_objects"] = len(ts._objects)
         return m
@@ -353,12 +342,12 @@ def _first_difference(meta, ts):
         if (meta.get(k) is None) != (obj is None):
             return "%s is %r, and the step has %s %s" % (k, meta.get(k), "no" if obj is None else "a", what)
     moved = meta.get("moved", [])
-    if not isinstance(moved, list) or any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < len(ts._objects) for i in moved):
+    if not isinstance(moved, list) or not all(_capi.int_in(i, 0, len(ts._objects)) for i in moved):
         return "moved is %r, the step's model has %d stacks and convs" % (moved, len(ts._objects))
     if moved and meta.get("range_objects") != len(ts._objects):
         return "moved counts among %r stacks and convs, the step's model has %d" % (meta.get("range_objects"), len(ts._objects))
     for k in ("steps", "skipped"):
-        if isinstance(meta.get(k), bool) or not isinstance(meta.get(k), int) or meta[k] < 0:
+        if not _capi.int_in(meta.get(k), 0):
             return "%s is %r" % (k, meta.get(k))
     return None
 
@@ -400,7 +389,7 @@ def restore(ts, ck):
     ts._skip_base = int(meta["skipped"]) - ts._count()
     for i in meta.get("moved", []):
         ts._objects[i].set_precision("bf16x3")
-        ts._seen.add(i)
+    ts._seen.update(meta.get("moved", []))
     if meta.get("moved") and ts._graph is not None:
         ts._stale = True
     ts._reset_record()

@@ -1,7 +1,7 @@
 // iaf_kernels_data.hpp -- the device-resident dataset: one launch gathers the next shuffled batch out of an image array in device memory
 // (include/iaf_hip.h: iaf_data_next_batch).  The reference keeps its training set in the graph and pulls a shuffled batch
 // out of it per step (tf_utils/cifar10_data.py:108-112, tf_utils/data_utils.py:29-36); this is the engine's counterpart, reproducible
-// from (seed, step, row).  Part of the single translation unit iaf_engine.hip (included there behind iaf_kernels_rng.hpp, whose
+// from (seed, step, row).  Part of the translation unit iaf_train_services.hip (included there and nowhere else, behind iaf_kernels_rng.hpp, whose
 // Philox4x32-10 is the round function here; not a standalone header).
 #pragma once
 

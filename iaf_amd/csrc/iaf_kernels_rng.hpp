@@ -1,7 +1,7 @@
 // iaf_kernels_rng.hpp -- the device noise source: Philox4x32-10 counters -> Box-Muller normals, one launch per LIST of tensors
 // (include/iaf_hip.h: iaf_rng_fill_normal).  The reference draws its noise inside the graph
 // (tf_utils/distributions.py:15-24); this is the engine's counterpart, reproducible from (seed, substream, step, element index).
-// Part of the single translation unit iaf_engine.hip (included there, in order; not a standalone header).
+// Part of the translation unit iaf_train_services.hip (included there and nowhere else, behind iaf_hip.h; not a standalone header).
 #pragma once
 
 // (IAF_RNG_MAX_TENSORS: include/iaf_hip.h)

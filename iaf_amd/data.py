@@ -10,8 +10,6 @@ numpy).  It is a keyed pseudo-random permutation, NOT a uniform draw from the n!
 
 The step counter lives in device memory: a gather reads it and, with advance=True, a one-thread launch behind it adds one -- so a
 captured graph that holds a gather trains on the next batch at every replay, and the host is out of the loop for whole epochs."""
-import ctypes
-
 import torch
 
 from . import _capi
@@ -19,31 +17,25 @@ from . import _capi
 MAX_BATCH = 65535
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _int_in(v, lo, hi):
-    return not isinstance(v, bool) and isinstance(v, int) and lo <= v < hi
-
-
-class DeviceDataset(object):
+class DeviceDataset(_capi.StepCounter):
     """ds = DeviceDataset(images, seed); x = ds.next_batch(B) gathers the batch of the current step and advances the step by one.
 
     images: a contiguous uint8 [n,3,S,S] device tensor, 1 <= n < 2**32; kept alive by the object and never copied (do not write to it
     while batches are drawn).  seed: 0 <= seed < 2**64 (a NoiseSource of the same seed shares no stream with it).
     deterministic=True (the reference's flag, used by its eval loop): the images in order, restarting at 0 after every epoch.
     rank, world: data-parallel ranks share images, seed and B and take disjoint rows of every global batch without talking.
-    Drive one dataset from one stream at a time."""
+    Drive one dataset from one stream at a time.
+    seek / skip / tell (_capi.StepCounter): the step the next gather draws at."""
+    _prefix = "iaf_data"
 
     def __init__(self, images, seed, deterministic=False, rank=0, world=1):
-        if not _int_in(seed, 0, 1 << 64):
+        if not _capi.int_in(seed, 0, 1 << 64):
             raise ValueError("seed must be an int in [0, 2**64), got %r" % (seed,))
         if not isinstance(deterministic, bool):
             raise ValueError("deterministic must be True or False, got %r" % (deterministic,))
-        if not _int_in(world, 1, 1 << 31):
+        if not _capi.int_in(world, 1, 1 << 31):
             raise ValueError("world must be a positive int, got %r" % (world,))
-        if not _int_in(rank, 0, world):
+        if not _capi.int_in(rank, 0, world):
             raise ValueError("rank must be an int in [0, world), got %r" % (rank,))
         if not (torch.is_tensor(images) and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[1] == 3
                 and images.shape[2] == images.shape[3] and images.is_contiguous()) or not images.is_cuda:
@@ -55,14 +47,12 @@ class DeviceDataset(object):
         self.n = int(images.shape[0])
         self.image_shape = tuple(int(v) for v in images.shape[1:])
         self.bytes_per_image = 3 * self.image_shape[1] * self.image_shape[2]
-        h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _capi.check(_capi.lib().iaf_data_create(ctypes.byref(h), ctypes.c_void_p(images.data_ptr()), self.n, self.bytes_per_image,
-                                                    seed, int(deterministic)))
-        self._h = h
+            self._own = _capi.Handle("iaf_data_create", _capi.ptr(images), self.n, self.bytes_per_image, seed, int(deterministic))
+        self._h = self._own.h
 
     def _check_batch(self, B):
-        if not _int_in(B, 1, MAX_BATCH + 1):
+        if not _capi.int_in(B, 1, MAX_BATCH + 1):
             raise ValueError("B must be an int in [1, %d], got %r" % (MAX_BATCH, B))
         if B * self.world > self.n:
             raise ValueError("a global batch of %d x %d rows is more than the dataset's %d images" % (B, self.world, self.n))
@@ -88,36 +78,10 @@ class DeviceDataset(object):
             if not (torch.is_tensor(indices) and indices.dtype == torch.int64 and tuple(indices.shape) == (B,)
                     and indices.is_contiguous()) or indices.device != self.device:
                 raise ValueError("next_batch: indices must be a contiguous int64 [%d] tensor on %s" % (B, self.device))
-            ip = ctypes.c_void_p(indices.data_ptr())
+            ip = _capi.ptr(indices)
             written = (out, indices)
-        _capi.check(_capi.lib().iaf_data_next_batch(self._h, ctypes.c_void_p(out.data_ptr()), ip, B, self.rank, self.world,
-                                                    int(bool(advance)), _stream()))
+        _capi.check(_capi.lib().iaf_data_next_batch(self._h, _capi.ptr(out), ip, B, self.rank, self.world,
+                                                    int(bool(advance)), _capi.stream()))
         # (raw-pointer writes: tell torch)
         torch.autograd.graph.increment_version(written)
         return out
-
-    def seek(self, step):
-        """set the step counter (enqueued on the current stream)"""
-        if not _int_in(step, 0, 1 << 64):
-            raise ValueError("step must be an int in [0, 2**64), got %r" % (step,))
-        _capi.check(_capi.lib().iaf_data_seek(self._h, step, _stream()))
-
-    def skip(self, steps=1):
-        """add `steps` to the step counter (enqueued on the current stream)"""
-        if not _int_in(steps, 0, 1 << 64):
-            raise ValueError("steps must be an int in [0, 2**64), got %r" % (steps,))
-        _capi.check(_capi.lib().iaf_data_skip(self._h, steps, _stream()))
-
-    def tell(self):
-        """the step the next gather on the current stream will draw at (synchronises that stream; not during a capture)"""
-        v = ctypes.c_uint64()
-        _capi.check(_capi.lib().iaf_data_tell(self._h, ctypes.byref(v), _stream()))
-        return int(v.value)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _capi.destroy("iaf_data_destroy", self._h)
-                self._h = None
-        except Exception:
-            pass

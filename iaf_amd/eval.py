@@ -9,27 +9,18 @@ on the images only) -- followed by k PASSES: one draw of posterior noise, the to
 running log-sum-exp and, on the k-th pass, closes the batch into a 32-byte device record.  The dataset's and the source's step
 counters and the record's pass counter live in device memory, so head and pass are captured ONCE each (two hipGraphs without
 parallel branches) and a batch is 1 + k replays; the host reads nothing until the epoch's last launch has run."""
-import ctypes
 import math
 import warnings
 
 import torch
 
-from . import _capi
+from . import _capi, _recover
+from ._capi import ptr as _ptr, stream as _stream
 from .data import MAX_BATCH, DeviceDataset
 from .model import CVAE1
 from .noise import NoiseSource
-from .train import _SWITCHED, _range_objects
 
 BINSIZE = 1 / 256.0
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class EvalPass(object):
@@ -69,7 +60,7 @@ class EvalPass(object):
             raise ValueError("EvalPass: data must be a DeviceDataset, got %r" % (data,))
         if data.world != 1:
             raise ValueError("EvalPass: the dataset was built for a world of %d (multi-rank evaluation is not covered)" % data.world)
-        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or not 1 <= batch_size <= MAX_BATCH:
+        if not _capi.int_in(batch_size, 1, MAX_BATCH + 1):
             raise ValueError("EvalPass: batch_size must be an int in [1, %d], got %r" % (MAX_BATCH, batch_size))
         if data.n % batch_size:
             raise ValueError("EvalPass: the dataset's %d images are no multiple of batch_size %d (tf_train.py:313)" % (data.n, batch_size))
@@ -77,7 +68,7 @@ class EvalPass(object):
             raise ValueError("EvalPass: images of shape %r, model built for %d" % (data.image_shape, model.image_size))
         if not isinstance(noise_source, NoiseSource):
             raise ValueError("EvalPass: noise_source must be a NoiseSource, got %r" % (noise_source,))
-        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        if not _capi.int_in(k, 1):
             raise ValueError("EvalPass: k must be a positive int, got %r" % (k,))
         if not isinstance(graph, bool) or not isinstance(per_image, bool):
             raise ValueError("EvalPass: graph and per_image must be True or False")
@@ -95,7 +86,7 @@ class EvalPass(object):
         self._graphs = None               # (head, pass)
         self._kept = None                 # what the captured head left for the captured pass
         self._stream = torch.cuda.Stream(device=dev) if graph else None
-        self._objects = _range_objects(model)
+        self._objects = _recover.range_objects(model)
         self._seen = set()                # range objects already moved to bf16 planes
 
     # -- the launches -------------------------------------------------------------------------------------------------------------
@@ -127,8 +118,7 @@ class EvalPass(object):
         S = m.image_size
         _capi.check(_capi.lib().iaf_eval_tail(_ptr(x_out), _ptr(m.params["dec_log_stdv"]), _ptr(xf), 3 * S * S, BINSIZE, _ptr(costs),
                                               int(costs.shape[0]), B, _ptr(b["run_max"]), _ptr(b["run_sum"]), self.k,
-                                              None if b["idx"] is None else _ptr(b["idx"]),
-                                              None if self.per_image is None else _ptr(self.per_image), _ptr(b["bound"]), _ptr(b["rec"]),
+                                              _ptr(b["idx"]), _ptr(self.per_image), _ptr(b["bound"]), _ptr(b["rec"]),
                                               _stream()))
         torch.autograd.graph.increment_version((b["run_max"], b["run_sum"], b["bound"], b["rec"]) +
                                                (() if self.per_image is None else (self.per_image,)))
@@ -140,62 +130,33 @@ class EvalPass(object):
 
     def _move(self):
         """Compute-only eager batches (one head, one pass; neither the dataset nor the source advances) until two in a row report
-        nothing, as TrainStep._move: each report moves one object to bf16 planes, and a pass on the new kernels can overflow further
-        down, which the pass after it reports.  Also the warm-up that precedes every capture."""
-        clean, limit = 0, 2 * len(self._objects) + 4
-        for _ in range(limit):
-            torch.cuda.synchronize()
-            try:
-                self.model.prepare_weights()
-                self._head(advance=False)
-                self._pass(advance=False)
-                clean += 1
-            except _SWITCHED:
-                clean = 0
-            if clean == 2:
-                torch.cuda.synchronize()
-                return
-        raise _capi.IafHipError("EvalPass: objects kept reporting range / exchange failures after %d passes" % limit)
+        nothing (_recover.settle, as TrainStep._move).  Also the warm-up that precedes every capture."""
+        def batch():
+            self.model.prepare_weights()
+            self._head(advance=False)
+            self._pass(advance=False)
+        _recover.settle(batch, len(self._objects), "EvalPass")
 
     def _state(self):
         return [(po.qz_mean, po.qz_logsd, po.up_context) for po in (layer.posterior for level in self.model.layers for layer in level)]
 
     def _capture(self):
         self._graphs = self._kept = None
-        s = self._stream
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for attempt in range(2):
-                self._move()
-                gh, gp = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                try:
-                    with torch.cuda.graph(gh, stream=s, capture_error_mode="thread_local"):
-                        self._head()
-                    kept = (self._buf["xf"], self._state())       # (the pass below is captured on exactly these tensors)
-                    with torch.cuda.graph(gp, stream=s, capture_error_mode="thread_local"):
-                        self._pass()
-                except _SWITCHED:
-                    torch.cuda.synchronize()
-                    continue
-                except Exception as e:       # noqa: BLE001
-                    self.graph_refused = (str(e).splitlines() or [""])[0]
-                    warnings.warn("EvalPass: the runtime refused to capture the evaluation (%s): eager launches" % self.graph_refused,
-                                  RuntimeWarning, stacklevel=4)
-                    torch.cuda.synchronize()
-                    break
-                self._graphs, self._kept = (gh, gp), kept
-                self.captures["head"] += 1
-                self.captures["pass"] += 1
-                break
-        torch.cuda.current_stream().wait_stream(s)
-        if self._graphs is None and self.graph_refused is None:
-            raise _capi.IafHipError("EvalPass: the capture kept meeting objects that switch kernels")
+
+        def head():
+            self._head()
+            return self._buf["xf"], self._state()       # (Python references: the pass is captured on exactly these tensors)
+        done = _recover.capture(self, self._stream, self._move, [head, self._pass], "EvalPass", "the evaluation", stacklevel=5)
+        if done is not None:
+            self._graphs, self._kept = tuple(done[0]), done[1][0]
+            self.captures["head"] += 1
+            self.captures["pass"] += 1
 
     def _run_once(self, nb):
         b, k = self._buffers(), self.k
         try:
             self.model.prepare_weights()
-        except _SWITCHED:                 # an object reports an EARLIER launch of somebody else's: move it before anything is enqueued
+        except _recover.SWITCHED:         # an object reports an EARLIER launch of somebody else's: move it before anything is enqueued
             self._move()
             self._graphs = self._kept = None
         if self.use_graph and self.graph_refused is None and self._graphs is None:
@@ -223,15 +184,13 @@ class EvalPass(object):
     def run(self, batches=None):
         nb = self.data.n // self.batch_size
         if batches is not None:
-            if isinstance(batches, bool) or not isinstance(batches, int) or not 1 <= batches <= nb:
+            if not _capi.int_in(batches, 1, nb + 1):
                 raise ValueError("EvalPass.run: batches must be an int in [1, %d], got %r" % (nb, batches))
             nb = batches
         noise_step = self.noise_source.tell()
         loss, images, nonfinite = self._run_once(nb)
         if nonfinite > 0:
-            flagged = {i for i, o in enumerate(self._objects) if o.range_errors()}
-            new = flagged - self._seen
-            self._seen |= flagged
+            new = _recover.newly_flagged(self._objects, self._seen)
             if new:
                 warnings.warn("EvalPass: %d of %d bounds were not finite and %d object(s) met an operand beyond fp16's range: they move to "
                               "bf16 planes and the run is repeated" % (nonfinite, images, len(new)), RuntimeWarning, stacklevel=2)

@@ -92,12 +92,7 @@ def variable_scope(name, store=None):
 # ---------------------------------------------------------------------------------------------
 # the engine-backed operator
 # ---------------------------------------------------------------------------------------------
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_ptr, _stream = _capi.ptr, _capi.stream          # (read from outside the package under these names)
 
 
 def _check_act(t, name, shape=None):
@@ -131,21 +126,13 @@ class ARStack(object):
             raise ValueError("the gfx950 engine implements the (mean, logsd) output pair n_out=[n_z, n_z]")
         self.n_z, self.n_h_list, self.depth_ar = int(n_z), n_h, len(n_h)
         self.n_h = int(n_h[0]) if n_h else int(n_z)
-        self._h = ctypes.c_void_p()
-        _capi.check(_capi.lib().iaf_stack_create(ctypes.byref(self._h), self.n_z, self.n_h, self.depth_ar, variant))
+        self._own = _capi.Handle("iaf_stack_create", self.n_z, self.n_h, self.depth_ar, variant)
+        self._h = self._own.h
         if os.environ.get("IAF_PRECISION"):          # process-wide override of the default (bf16x3): "f32" | "bf16x3"
             self.set_precision(os.environ["IAF_PRECISION"])
         self._ws = None
         self._prep_key = None
         self._keepalive = None
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _capi.destroy("iaf_stack_destroy", h)
-            except Exception:
-                pass
 
     # -- weights -------------------------------------------------------------------------------
     def conv_names(self):
@@ -610,28 +597,18 @@ class WNConv2d(object):
         theano=True (masked only): the Theano statement, N.ar.conv2d (graphy/nodes/ar.py:200-375), optionally flipmask;
         prepare() then takes (w OIHW [n_out, n_in+1, 3, 3], s, b)."""
         self.n_in, self.n_out, self.ar_mask, self.theano = int(n_in), int(n_out), ar_mask, bool(theano)
-        self._h = ctypes.c_void_p()
         if theano:
             if ar_mask is None:
                 raise ValueError("theano=True is the masked conv N.ar.conv2d: pass ar_mask=False/True (zerodiagonal)")
-            _capi.check(_capi.lib().iaf_conv3x3_create_masked_theano(ctypes.byref(self._h), self.n_in, self.n_out,
-                                                                     1 if ar_mask else 0, 1 if flipmask else 0))
+            self._own = _capi.Handle("iaf_conv3x3_create_masked_theano", self.n_in, self.n_out, 1 if ar_mask else 0, 1 if flipmask else 0)
         elif ar_mask is None:
-            _capi.check(_capi.lib().iaf_conv3x3_create(ctypes.byref(self._h), self.n_in, self.n_out))
+            self._own = _capi.Handle("iaf_conv3x3_create", self.n_in, self.n_out)
         else:
-            _capi.check(_capi.lib().iaf_conv3x3_create_masked(ctypes.byref(self._h), self.n_in, self.n_out,
-                                                              1 if ar_mask else 0))
+            self._own = _capi.Handle("iaf_conv3x3_create_masked", self.n_in, self.n_out, 1 if ar_mask else 0)
+        self._h = self._own.h
         self._tuned, self._cur_tune = {}, None      # (B,H,W) -> launch shape found by autotune
         self._prep_key = None
         self._keepalive = None
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _capi.destroy("iaf_conv3x3_destroy", h)
-            except Exception:
-                pass
 
     def prepare(self, V, g, b, force=False):
         """V HWIO [3,3,n_in,n_out], g/b [n_out] (layers.py:53-55); cached until a tensor is replaced or modified.
@@ -947,7 +924,7 @@ MAX_FREE_BITS_GROUPS = 64       # IAF_MAX_FREE_BITS_GROUPS (include/iaf_hip.h)
 
 def check_groups(n, what="groups"):
     """a number of free-bits row groups / towers: an int (no bool) in 1 .. MAX_FREE_BITS_GROUPS"""
-    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_FREE_BITS_GROUPS:
+    if not _capi.int_in(n, 1, MAX_FREE_BITS_GROUPS + 1):
         raise ValueError("%s must be an int in 1 .. %d, got %r" % (what, MAX_FREE_BITS_GROUPS, n))
     return n
 
@@ -985,17 +962,9 @@ class PrepBatch(object):
     def __init__(self, stacks):
         self.stacks = list(stacks)
         arr = (ctypes.c_void_p * len(self.stacks))(*[s._h.value for s in self.stacks])
-        self._h = ctypes.c_void_p()
-        _capi.check(_capi.lib().iaf_prep_batch_create(ctypes.byref(self._h), arr, len(self.stacks)))
+        self._own = _capi.Handle("iaf_prep_batch_create", arr, len(self.stacks))
+        self._h = self._own.h
         self._keepalive = None
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _capi.destroy("iaf_prep_batch_destroy", h)
-            except Exception:
-                pass
 
     def run(self, params_list):
         tens = []
@@ -1018,17 +987,9 @@ class ConvPrepBatch(object):
     def __init__(self, convs):
         self.convs = list(convs)
         arr = (ctypes.c_void_p * len(self.convs))(*[c._h.value for c in self.convs])
-        self._h = ctypes.c_void_p()
-        _capi.check(_capi.lib().iaf_conv3x3_prep_batch_create(ctypes.byref(self._h), arr, len(self.convs)))
+        self._own = _capi.Handle("iaf_conv3x3_prep_batch_create", arr, len(self.convs))
+        self._h = self._own.h
         self._keepalive = None
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _capi.destroy("iaf_conv3x3_prep_batch_destroy", h)
-            except Exception:
-                pass
 
     def run(self, vgb_list):
         """vgb_list: one (V, g, b) tuple of device tensors per conv, in construction order."""
@@ -1062,23 +1023,14 @@ class WnBwdBatch(object):
             for st in self.stacks:
                 _capi.check(lib.iaf_stack_set_defer_weightnorm(st._h, 1))
             arr = (ctypes.c_void_p * len(self.stacks))(*[st._h.value for st in self.stacks])
-            self._hs = ctypes.c_void_p()
-            _capi.check(lib.iaf_wn_bwd_batch_create(ctypes.byref(self._hs), arr, len(self.stacks)))
+            self._own_s = _capi.Handle("iaf_wn_bwd_batch_create", arr, len(self.stacks))
+            self._hs = self._own_s.h
         if self.convs:
             for c in self.convs:
                 _capi.check(lib.iaf_conv3x3_set_defer_weightnorm(c._h, 1))
             arr = (ctypes.c_void_p * len(self.convs))(*[c._h.value for c in self.convs])
-            self._hc = ctypes.c_void_p()
-            _capi.check(lib.iaf_conv3x3_wn_bwd_batch_create(ctypes.byref(self._hc), arr, len(self.convs)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_hs", None):
-                _capi.destroy("iaf_wn_bwd_batch_destroy", self._hs)
-            if getattr(self, "_hc", None):
-                _capi.destroy("iaf_conv3x3_wn_bwd_batch_destroy", self._hc)
-        except Exception:
-            pass
+            self._own_c = _capi.Handle("iaf_conv3x3_wn_bwd_batch_create", arr, len(self.convs))
+            self._hc = self._own_c.h
 
     @staticmethod
     def _tables(tens):

@@ -224,7 +224,7 @@ class CVAE1(object):
     def noise_shapes(self, B):
         """Host bookkeeping: the shapes of forward()'s noise list for a batch of B images -- per layer in top-down order (eps_prior,
         eps_post), B * k rows each."""
-        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+        if not _capi.int_in(B, 1):
             raise ValueError("B must be a positive int, got %r" % (B,))
         return self._noise_shapes(B * self.k)
 
@@ -267,7 +267,7 @@ class CVAE1(object):
     def sample(self, B, source, temperature=1.0):
         """B images from the prior with noise from `source` (one step of it): draw_noise(which="prior") + generate().  No host
         synchronisation: capturable, and a replay draws fresh noise."""
-        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+        if not _capi.int_in(B, 1):
             raise ValueError("B must be a positive int, got %r" % (B,))
         return self.generate(self.draw_noise(B, source, which="prior", temperature=temperature, _rows=B)[0::2])
 
@@ -288,7 +288,7 @@ class CVAE1(object):
         if noise_source is None:
             if k is not None:
                 raise ValueError("iw_eval: k goes with noise_source (noise_passes carries its own length)")
-        elif isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        elif not _capi.int_in(k, 1):
             raise ValueError("iw_eval: k must be a positive int with noise_source, got %r" % (k,))
         if not torch.is_tensor(x) or x.dim() != 4:
             raise ValueError("x must be a contiguous uint8 [B,3,S,S] device tensor")

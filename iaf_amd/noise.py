@@ -14,22 +14,20 @@ MAX_TENSORS = 64
 MAX_COUNT = 1 << 34
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class NoiseSource(object):
+class NoiseSource(_capi.StepCounter):
     """src = NoiseSource(seed); src.fill([t0, t1, ...]) fills contiguous fp32 device tensors with N(0,1) noise at the current step
     and advances the step by one.
 
     seed: 0 <= seed < 2**64.  device: the device the counter lives on (default: the current one); tensors must be on it.
     substream_base: the substream of the first tensor of a list (the others follow); data-parallel ranks share the seed and use
-    substream_base = rank << 16.  Drive one source from one stream at a time."""
+    substream_base = rank << 16.  Drive one source from one stream at a time.
+    seek / skip / tell (_capi.StepCounter): the step the next fill draws at."""
+    _prefix = "iaf_rng"
 
     def __init__(self, seed, device=None, substream_base=0):
-        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        if not _capi.int_in(seed, 0, 1 << 64):
             raise ValueError("seed must be an int in [0, 2**64), got %r" % (seed,))
-        if isinstance(substream_base, bool) or not isinstance(substream_base, int) or not 0 <= substream_base < 1 << 32:
+        if not _capi.int_in(substream_base, 0, 1 << 32):
             raise ValueError("substream_base must be an int in [0, 2**32), got %r" % (substream_base,))
         self.seed, self.substream_base = seed, substream_base
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -37,10 +35,9 @@ class NoiseSource(object):
             raise ValueError("NoiseSource lives on a GPU, got device %r" % (device,))
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _capi.check(_capi.lib().iaf_rng_create(ctypes.byref(h), seed))
-        self._h = h
+            self._own = _capi.Handle("iaf_rng_create", seed)
+        self._h = self._own.h
 
     def fill(self, tensors, substreams=None, scales=None, advance=True):
         """tensors[i] <- scales[i] * N(0,1) at the current step, substream substreams[i] (default substream_base + i; scales default 1).
@@ -59,9 +56,9 @@ class NoiseSource(object):
             if not 1 <= t.numel() <= MAX_COUNT:
                 raise ValueError("fill: tensors[%d] has %d elements (1 .. 2**34)" % (i, t.numel()))
             s = substreams[i]
-            if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < 1 << 32:
+            if not _capi.int_in(s, 0, 1 << 32):
                 raise ValueError("fill: substreams[%d] must be an int in [0, 2**32), got %r" % (i, s))
-        lib, st = _capi.lib(), _stream()
+        lib, st = _capi.lib(), _capi.stream()
         for lo in range(0, n, MAX_TENSORS):
             hi = min(n, lo + MAX_TENSORS)
             m = hi - lo
@@ -73,29 +70,3 @@ class NoiseSource(object):
         # (raw-pointer writes: tell torch)
         torch.autograd.graph.increment_version(tuple(tensors))
         return tensors
-
-    def seek(self, step):
-        """set the step counter (enqueued on the current stream)"""
-        if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 1 << 64:
-            raise ValueError("step must be an int in [0, 2**64), got %r" % (step,))
-        _capi.check(_capi.lib().iaf_rng_seek(self._h, step, _stream()))
-
-    def skip(self, steps=1):
-        """add `steps` to the step counter (enqueued on the current stream)"""
-        if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps < 1 << 64:
-            raise ValueError("steps must be an int in [0, 2**64), got %r" % (steps,))
-        _capi.check(_capi.lib().iaf_rng_skip(self._h, steps, _stream()))
-
-    def tell(self):
-        """the step the next fill on the current stream will draw at (synchronises that stream; not during a capture)"""
-        v = ctypes.c_uint64()
-        _capi.check(_capi.lib().iaf_rng_tell(self._h, ctypes.byref(v), _stream()))
-        return int(v.value)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _capi.destroy("iaf_rng_destroy", self._h)
-                self._h = None
-        except Exception:
-            pass

@@ -5,10 +5,13 @@ plain `+` ops.  Here every rank owns a full parameter replica in HBM; the only e
 all-reduce(sum) over a flat fp32 gradient bucket followed by 1/N (== average_dense, common.py:83-86), done by
 RCCL over xGMI (torch.distributed backend "nccl") or gloo on CPU.  The forward IAF path needs no collective:
 every sample is independent and the free-bits mean is over the LOCAL tower batch (tf_train.py:79)."""
+import ctypes
 import math
 
 import torch
 import torch.distributed as dist
+
+from . import _capi
 
 
 class RcclComm(object):
@@ -18,9 +21,6 @@ class RcclComm(object):
     the 128-byte communicator id from rank 0 to the others; no collective of the training loop goes through it."""
 
     def __init__(self, group=None, device=None):
-        import ctypes
-        from . import _capi
-        self._capi, self._ct = _capi, ctypes
         lib = _capi.lib()
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -32,14 +32,13 @@ class RcclComm(object):
             box = [bytes(idbuf.raw)]
             dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
             idbuf = ctypes.create_string_buffer(box[0], _capi.IAF_COMM_ID_BYTES)
-        h = ctypes.c_void_p()
-        _capi.check(lib.iaf_comm_create(ctypes.byref(h), idbuf, self.rank, self.world, self.device))
-        self._h = h
+        self._own = _capi.Handle("iaf_comm_create", idbuf, self.rank, self.world, self.device)
+        self._h = self._own.h
         self.library = lib.iaf_comm_library().decode()
 
     def size(self):
-        r, w = self._ct.c_int(), self._ct.c_int()
-        self._capi.check(self._capi.lib().iaf_comm_size(self._h, self._ct.byref(r), self._ct.byref(w)))
+        r, w = ctypes.c_int(), ctypes.c_int()
+        _capi.check(_capi.lib().iaf_comm_size(self._h, ctypes.byref(r), ctypes.byref(w)))
         return r.value, w.value
 
     def all_reduce_sum_(self, t, stream=None):
@@ -47,19 +46,11 @@ class RcclComm(object):
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
             raise ValueError("all_reduce_sum_ takes a contiguous fp32 device tensor")
         st = torch.cuda.current_stream() if stream is None else stream
-        self._capi.check(self._capi.lib().iaf_allreduce_sum_f32(self._h, self._ct.c_void_p(t.data_ptr()), t.numel(),
-                                                                self._ct.c_void_p(st.cuda_stream)))
+        _capi.check(_capi.lib().iaf_allreduce_sum_f32(self._h, _capi.ptr(t), t.numel(), ctypes.c_void_p(st.cuda_stream)))
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._capi.destroy("iaf_comm_destroy", self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._own.close()
+        self._h = None
 
 
 class FlatParams(object):
@@ -105,13 +96,10 @@ class FlatParams(object):
 
     def adamax_ema_step(self, lr, world=1, beta1=0.9, beta2=0.999, eps=1e-8, ema_decay=0.999):
         if self.params.is_cuda:
-            import ctypes
-            from . import _capi
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+            ptr = _capi.ptr
             _capi.check(_capi.lib().iaf_adamax_ema_step(ptr(self.params), ptr(self.grads), ptr(self.slot_m), ptr(self.slot_v),
                                                         ptr(self.ema), self.params.numel(), lr, beta1, beta2, eps, ema_decay,
-                                                        1.0 / world,
-                                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                                        1.0 / world, _capi.stream()))
             # the launch wrote through raw pointers: tell torch, so that (data_ptr, _version)-keyed caches downstream
             # (ARStack.prepare, WNConv2d.prepare, IAFLayer.load) see new weights.  Views share the base's counter.
             torch.autograd.graph.increment_version((self.params, self.ema, self.slot_m, self.slot_v))

@@ -21,27 +21,22 @@ step runs where it did not overflow."""
 import ctypes
 import inspect
 import math
-import warnings
 
 import torch
 import torch.distributed as dist
 
-from . import _capi
+from . import _capi, _recover
+from ._recover import SWITCHED as _SWITCHED, range_objects as _range_objects      # (read from outside under these names)
 from .layers import check_groups
 from .parallel import FlatParams, OverlappedGradReduce
-
-# the errors an object reports once, at its next eager call, about an EARLIER launch whose outputs carry inf / NaN; the object has
-# switched kernels and the call can be repeated
-_SWITCHED = (_capi.RangeError, _capi.ExchangeError)
 
 
 class _SkipCounter(object):
     """iaf_skip_counter_t: the number of updates the gated kernel skipped, in mapped host memory"""
 
     def __init__(self):
-        h = ctypes.c_void_p()
-        _capi.check(_capi.lib().iaf_skip_counter_create(ctypes.byref(h)))
-        self._h = h
+        self._own = _capi.Handle("iaf_skip_counter_create")
+        self._h = self._own.h
 
     def read(self):
         """the count as far as the device has got (no synchronisation)"""
@@ -49,23 +44,9 @@ class _SkipCounter(object):
         _capi.check(_capi.lib().iaf_skip_counter_read(self._h, ctypes.byref(c)))
         return c.value
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _capi.destroy("iaf_skip_counter_destroy", self._h)
-                self._h = None
-        except Exception:
-            pass
-
-
-def _range_objects(model):
-    """the stacks and convs of a CVAE1 that keep a range word (an object without `layers` has none)"""
-    out = []
-    for level in getattr(model, "layers", []):
-        for layer in level:
-            out.append(layer.posterior.stack)
-            out.extend(layer.convs())
-    return out
+    def counter_ptr(self):
+        """the count's device address (what a state snapshot copies)"""
+        return _capi.counter_address("iaf_skip_counter_ptr", self._h)
 
 
 class TrainStep(object):
@@ -119,7 +100,7 @@ class TrainStep(object):
                  noise_source=None, summaries=False, data=None, batch_size=None):
         if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0:
             raise ValueError("lr must be a positive finite number, got %r" % (lr,))
-        if isinstance(n_buckets, bool) or not isinstance(n_buckets, int) or n_buckets < 1:
+        if not _capi.int_in(n_buckets, 1):
             raise ValueError("n_buckets must be a positive int, got %r" % (n_buckets,))
         if not isinstance(graph, bool):
             raise ValueError("graph must be True or False, got %r" % (graph,))
@@ -134,7 +115,7 @@ class TrainStep(object):
             from .data import DeviceDataset
             if not isinstance(data, DeviceDataset):
                 raise ValueError("data must be a DeviceDataset, got %r" % (data,))
-            if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            if not _capi.int_in(batch_size, 1):
                 raise ValueError("TrainStep(data=): batch_size must be a positive int, got %r" % (batch_size,))
             data.batches_per_epoch(batch_size)          # (ValueError: a global batch larger than the dataset)
         elif batch_size is not None:
@@ -304,9 +285,7 @@ class TrainStep(object):
         flat, (b1, b2, eps, decay) = self.flat, self._hyper
         summ = self.with_summaries and self._terms is not None      # (no terms: the very first step could not finish its compute)
         if self.on_device:
-            lib = _capi.lib()
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            lib, ptr, st = _capi.lib(), _capi.ptr, _capi.stream()
             if summ:
                 t, (nl, n) = self._terms, self._geom
                 _capi.check(lib.iaf_nonfinite_scan_sumsq(ptr(flat.grads), flat.grads.numel(), ptr(self._status), 1, ptr(self._guard),
@@ -347,57 +326,23 @@ class TrainStep(object):
         if self.on_device:
             torch.cuda.synchronize()
         self._acted = self._count()
-        flagged = {i for i, o in enumerate(self._objects) if o.range_errors()}
-        new = flagged - self._seen
-        self._seen |= flagged
+        new = _recover.newly_flagged(self._objects, self._seen)
         moved, self._aborted = self._aborted or bool(new), False
         return moved
 
     def _move(self, x, noise):
-        """Compute-only eager passes on (x, noise) until two in a row report nothing: each report moves one object to bf16 planes
-        (existing protocol), and a pass on the new kernels can overflow further down, which the pass after it reports."""
-        clean, limit = 0, 2 * len(self._objects) + 4
-        for _ in range(limit):
-            if self.on_device:
-                torch.cuda.synchronize()
-            try:
-                self._compute(x, noise)
-                clean += 1
-            except _SWITCHED:
-                clean = 0
-            if clean == 2:
-                if self.on_device:
-                    torch.cuda.synchronize()
-                return
-        raise _capi.IafHipError("TrainStep: objects kept reporting range / exchange failures after %d passes" % limit)
+        """compute-only eager passes on (x, noise) until the objects that switch kernels have settled (_recover.settle)"""
+        _recover.settle(lambda: self._compute(x, noise), len(self._objects), "TrainStep", self.on_device)
 
     def _capture(self):
         self._graph = None
         x, noise = self._static
-        s = self._stream
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for attempt in range(2):
-                self._move(x, noise)         # (also the warm-up: workspaces, exchange sets and launch caches exist before the capture)
-                g = torch.cuda.CUDAGraph()
-                try:
-                    with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                        obj = self._enqueue(x, noise, draw=self.noise_source is not None, gather=self._static_gathers)
-                except _SWITCHED:
-                    torch.cuda.synchronize()
-                    continue
-                except Exception as e:       # noqa: BLE001
-                    self.graph_refused = (str(e).splitlines() or [""])[0]
-                    warnings.warn("TrainStep: the runtime refused to capture the step (%s): eager launches" % self.graph_refused,
-                                  RuntimeWarning, stacklevel=3)
-                    torch.cuda.synchronize()
-                    return
-                self._graph, self._sobj = g, obj
-                self.captures += 1
-                break
-        torch.cuda.current_stream().wait_stream(s)
-        if self._graph is None and self.graph_refused is None:
-            raise _capi.IafHipError("TrainStep: the capture kept meeting objects that switch kernels")
+        done = _recover.capture(self, self._stream, lambda: self._move(x, noise),
+                                [lambda: self._enqueue(x, noise, draw=self.noise_source is not None, gather=self._static_gathers)],
+                                "TrainStep", "the step", stacklevel=4)
+        if done is not None:
+            (self._graph,), (self._sobj,) = done
+            self.captures += 1
 
     # -- public ---------------------------------------------------------------------------------------------------------------------
     def _own_noise(self, x):
@@ -505,8 +450,7 @@ class TrainStep(object):
         if not self.with_summaries or self._rec is None:
             return
         if self.on_device:
-            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _capi.check(_capi.lib().iaf_train_summaries_reset(ctypes.c_void_p(self._rec.data_ptr()), self._geom[0], st))
+            _capi.check(_capi.lib().iaf_train_summaries_reset(_capi.ptr(self._rec), self._geom[0], _capi.stream()))
         else:
             self._rec.update(acc=torch.zeros_like(self._rec["acc"]), last=torch.zeros_like(self._rec["last"]), steps=0, skipped=0)
 

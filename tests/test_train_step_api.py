@@ -164,7 +164,7 @@ def test_guard_kernels_use_no_scratch(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_resources as kr
     src = tmp_path / "guard_kernels.hip"
-    src.write_text('#include <hip/hip_runtime.h>\n#include "iaf_conv_kernel.hpp"\n#include "iaf_kernels_misc.hpp"\n')
+    src.write_text('#include <hip/hip_runtime.h>\n#include "iaf_conv_kernel.hpp"\n#include "iaf_kernels_train.hpp"\n')
     rows = [r for r in kr.unit_resources(str(src), str(tmp_path / "guard_kernels.o"), [])
             if "nonfinite_scan" in r["name"] or "adamax_ema_guarded" in r["name"]]
     assert len(rows) == 2, [r["name"] for r in rows]
