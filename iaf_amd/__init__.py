@@ -14,9 +14,10 @@ from .model import CVAE1  # noqa: F401
 from .train import TrainStep  # noqa: F401
 from .noise import NoiseSource  # noqa: F401
 from .data import DeviceDataset  # noqa: F401
+from .images import grid_shape, image_grid, write_png  # noqa: F401
 from .eval import EvalPass  # noqa: F401
 from .checkpoint import Checkpoint, Snapshot, load_checkpoint, save_checkpoint  # noqa: F401
 
 __all__ = ["ExchangeError", "IafHipError", "UnsupportedError", "ARStack", "PrepBatch", "VariableStore", "ar_multiconv2d", "get_conv_ar_mask", "get_linear_ar_mask", "multiconv2d", "variable_scope",
            "default_store", "DiagonalGaussian", "compute_lowerbound", "gaussian_diag_logps", "logsumexp", "repeat",
-           "StreamingLowerBound", "IAFPosterior", "IAFLayer", "IWEvaluator", "CVAELayerIAF", "CVAE1", "TrainStep", "NoiseSource", "DeviceDataset", "EvalPass", "Checkpoint", "Snapshot", "load_checkpoint", "save_checkpoint", "WNConv2d", "ConvPrepBatch", "WnBwdBatch", "conv2d", "ar_conv2d", "discretized_logistic", "split", "resample2", "resize_nearest_neighbor", "ar_conv2d_theano"]
+           "StreamingLowerBound", "IAFPosterior", "IAFLayer", "IWEvaluator", "CVAELayerIAF", "CVAE1", "TrainStep", "NoiseSource", "DeviceDataset", "EvalPass", "grid_shape", "image_grid", "write_png", "Checkpoint", "Snapshot", "load_checkpoint", "save_checkpoint", "WNConv2d", "ConvPrepBatch", "WnBwdBatch", "conv2d", "ar_conv2d", "discretized_logistic", "split", "resample2", "resize_nearest_neighbor", "ar_conv2d_theano"]

@@ -41,6 +41,15 @@ class StatePart(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bytes", ctypes.c_size_t)]
 
 
+IAF_IMG_U8 = 0
+IAF_IMG_F32 = 1
+
+
+class ImgSource(ctypes.Structure):
+    """iaf_img_source_t: one source of iaf_img_grid (inner may be None)"""
+    _fields_ = [("ptr", ctypes.c_void_p), ("dtype", ctypes.c_int), ("outer", ctypes.c_void_p), ("inner", ctypes.c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/iaf_hip.h declares
 SIGNATURES = {
     "iaf_abi_version": (ctypes.c_int, []),
@@ -224,6 +233,8 @@ SIGNATURES = {
     "iaf_rng_step_ptr": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "iaf_data_step_ptr": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "iaf_skip_counter_ptr": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "iaf_img_range": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_size_t, _vp, _vp]),
+    "iaf_img_grid": (ctypes.c_int, [ctypes.POINTER(ImgSource)] + [ctypes.c_int] * 6 + [ctypes.c_float, _vp, _vp, _vp]),
     "iaf_conv3x3_work": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 2),
 }
 

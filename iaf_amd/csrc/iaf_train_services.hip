@@ -1,8 +1,10 @@
 // iaf_train_services.hip -- the services of the training loop that take no stack and no conv (C ABI: include/iaf_hip.h): Adamax + EMA,
-// the skip counter, the guard scans, the step's summaries, the device noise source, the device-resident dataset and the state snapshot.
+// the skip counter, the guard scans, the step's summaries, the device noise source, the device-resident dataset, the state snapshot
+// and run_eval's image grids.
 // A translation unit of its own beside iaf_engine.hip; its kernel headers are included here and nowhere else.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <new>
@@ -13,6 +15,7 @@
 #include "iaf_kernels_train.hpp"
 #include "iaf_kernels_rng.hpp"
 #include "iaf_kernels_data.hpp"
+#include "iaf_kernels_image.hpp"
 
 extern "C" int iaf_adamax_ema_step(float* var, const float* grad, float* slot_m, float* slot_v, float* ema, size_t n, float lr,
                                    float beta1, float beta2, float eps, float ema_decay, float grad_scale, void* stream) {
@@ -313,5 +316,56 @@ extern "C" int iaf_state_snapshot(const iaf_state_part_t* parts, int n_parts, ui
     if (e != hipSuccess) return (int)e;
     const unsigned grid = iaf_state_assign(T, IAF_STATE_MAX_BLOCKS);      // (the chip's share of workgroups, in proportion to the parts' sizes)
     hipLaunchKernelGGL(iaf_state_snapshot_kernel, dim3(grid), dim3(IAF_STATE_THREADS), 0, st, T, (unsigned long long*)digests);
+    return (int)hipGetLastError();
+}
+
+// run_eval's image summaries (iaf_kernels_image.hpp): the range of a slice into a 16-byte record, and the one launch that stretches and
+// tiles.  The source table travels in the kernel arguments, as the snapshot's part table does.
+extern "C" int iaf_img_range(const void* src, int dtype, size_t n_elems, void* record, void* stream) {
+    if (!src || !record) return IAF_ERR_NULL;
+    if ((dtype != IAF_IMG_U8 && dtype != IAF_IMG_F32) || n_elems == 0) return IAF_ERR_SHAPE;
+    if (((uintptr_t)record & 7) != 0 || (dtype == IAF_IMG_F32 && ((uintptr_t)src & 3) != 0)) return IAF_ERR_WORKSPACE;
+    const size_t per = dtype == IAF_IMG_U8 ? 16 : 4, esz = dtype == IAF_IMG_U8 ? 1 : 4;       // elements per 16-byte piece, bytes per element
+    size_t head = ((16 - ((uintptr_t)src & 15)) & 15) / esz;                                   // elements before src's first 16-byte boundary
+    if (head > n_elems) head = n_elems;
+    const size_t pieces = (n_elems - head) / per;
+    size_t grid = (pieces * 16 + IAF_IMG_RANGE_SHARE - 1) / IAF_IMG_RANGE_SHARE;
+    if (grid > IAF_IMG_RANGE_MAX_BLOCKS) grid = IAF_IMG_RANGE_MAX_BLOCKS;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(iaf_img_range_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, src, dtype, (unsigned long long)n_elems,
+                       (unsigned)head, (unsigned long long)pieces, (ImgRangeRec*)record);
+    return (int)hipGetLastError();
+}
+
+// the reference's grid of n tiles of H x W pixels at aspect_ratio 1.0 (include/iaf_hip.h states it; iaf_amd/images.py: grid_shape)
+static void img_grid_tiles(int n, int H, int W, int* th, int* tw) {
+    const double ar = 1.0 * ((double)W / (double)H);
+    *th = (int)ceil(sqrt((double)n * ar));
+    *tw = (int)ceil(sqrt((double)n / ar));
+}
+
+extern "C" int iaf_img_grid(const iaf_img_source_t* sources, int n_src, int n_imgs, int C, int H, int W, int border, float border_color,
+                            float* grid_f32, unsigned char* grid_u8, void* stream) {
+    if (!sources || (!grid_f32 && !grid_u8)) return IAF_ERR_NULL;
+    if (n_src < 1 || n_src > 2 || n_imgs < 1 || (C != 1 && C != 3) || H < 1 || W < 1 || border < 0) return IAF_ERR_SHAPE;
+    ImgGridTable T;
+    memset(&T, 0, sizeof(T));
+    for (int s = 0; s < n_src; ++s) {
+        if (!sources[s].ptr || !sources[s].outer) return IAF_ERR_NULL;
+        if (sources[s].dtype != IAF_IMG_U8 && sources[s].dtype != IAF_IMG_F32) return IAF_ERR_SHAPE;
+        if ((((uintptr_t)sources[s].outer | (uintptr_t)sources[s].inner) & 7) != 0) return IAF_ERR_WORKSPACE;
+        if (sources[s].dtype == IAF_IMG_F32 && ((uintptr_t)sources[s].ptr & 3) != 0) return IAF_ERR_WORKSPACE;
+        T.ptr[s] = sources[s].ptr;
+        T.dtype[s] = sources[s].dtype;
+        T.outer[s] = (const ImgRangeRec*)sources[s].outer;
+        T.inner[s] = (const ImgRangeRec*)sources[s].inner;
+    }
+    if (((uintptr_t)grid_f32 & 3) != 0) return IAF_ERR_WORKSPACE;
+    int th = 0, tw = 0;
+    img_grid_tiles(n_imgs, H, W, &th, &tw);
+    const long long Hg = ((long long)H + border) * th - border, Wg = ((long long)W + border) * tw - border;
+    if (Hg < 1 || Wg < 1 || Hg * Wg >= (1ll << 31) || (long long)th * tw < n_imgs) return IAF_ERR_SHAPE;
+    hipLaunchKernelGGL(iaf_img_grid_kernel, dim3((unsigned)((Hg * Wg + 255) / 256)), dim3(256), 0, (hipStream_t)stream, T, n_src, n_imgs, C, H, W,
+                       border, border_color, th, tw, (int)Hg, (int)Wg, grid_f32, grid_u8);
     return (int)hipGetLastError();
 }

@@ -17,6 +17,7 @@ import torch
 from . import _capi, _recover
 from ._capi import ptr as _ptr, stream as _stream
 from .data import MAX_BATCH, DeviceDataset
+from .images import image_grid
 from .model import CVAE1
 from .noise import NoiseSource
 
@@ -48,7 +49,9 @@ class EvalPass(object):
     A run that ends with nonfinite > 0 while a stack or conv of the model has newly raised its range word (an operand beyond
     65504 in a launch on two fp16 planes, include/iaf_hip.h) moves those objects to bf16 planes through the existing protocol --
     compute-only eager passes, then a new capture --, seeks the source back to noise_step and repeats the run ONCE behind a
-    RuntimeWarning; what the second run gives is returned as it is."""
+    RuntimeWarning; what the second run gives is returned as it is.
+
+    images(total=36, temperature=1.0): run_eval's reconstruction and sample grids (k = 1 only); see the method."""
 
     def __init__(self, model, data, batch_size, noise_source, k=1, graph=True, per_image=False):
         if not isinstance(model, CVAE1) or model.params is None:
@@ -202,6 +205,58 @@ class EvalPass(object):
         bpd = loss / (math.log(2.) * 3 * S * S * images) if images else float("nan")
         return {"eval_bits_per_dim": bpd, "loss": loss, "images": images, "batches": nb, "k": self.k, "nonfinite": nonfinite,
                 "noise_step": noise_step}
+
+    def images(self, total=36, temperature=1.0):
+        """run_eval's two pictures (tf_train.py:329-376; hps.k = 1 only): "reconstructions" -- total/2 images of the dataset's next batch
+        in the even slots, the model's reconstructions of them (the clipped x_dec output, m_trunc) in the odd ones, each stretched over
+        its own total/2 rows -- and "samples" -- `total` images from the prior at `temperature`, stretched over the batch of
+        batch_size rows they were drawn in and then over the `total` shown.  Both tiled with border 0 (iaf_amd/images.py).
+
+        Returns the two grids as host uint8 ndarrays [Hg,Wg,3] under those names (write_png takes them), "reconstructions_f32" /
+        "samples_f32" (the float grids in [0,1]), "inputs" (uint8 [total/2,3,S,S]), "x_mean" (fp32 [total/2,3,S,S]) and "x_gen" (fp32
+        [batch_size,3,S,S]) as device tensors, and "data_step", "noise_step", "nonfinite": the dataset's step the batch was gathered
+        at, the source's step of the posterior noise (the prior noise is the step behind it), and the number of non-finite elements
+        the stretches met -- > 0: the source concerned shows NaN / 0 in its slots, behind a RuntimeWarning.
+        The batch is the one at the dataset's current step, which advances by one: after run() on a deterministic dataset that is
+        the wrap to batch 0, as in the reference.  The source advances by two steps.  Eager launches on the current stream, the ones
+        CVAE1.forward and CVAE1.sample make: the epoch's record, per_image and the captured graphs are not touched.  One
+        synchronisation, at the final copy."""
+        if self.k != 1:
+            raise ValueError("EvalPass.images: the reference draws its pictures with k = 1 only (tf_train.py:329), this pass has k = %r" % (self.k,))
+        B = self.batch_size
+        if not _capi.int_in(total, 2, B + 1) or total % 2:
+            raise ValueError("EvalPass.images: total must be an even int in [2, batch_size = %d], got %r (a grid that spans several batches, "
+                             "each of which the reference stretches on its own, is not covered)" % (B, total))
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature):
+            raise ValueError("EvalPass.images: temperature must be a finite number, got %r" % (temperature,))
+        m, half = self.model, total // 2
+        lib = _capi.lib()
+        steps = torch.empty((2, 2), dtype=torch.int64, device=self.device)          # [0]: the two counters as they stand, [1]: their digests
+        parts = (_capi.StatePart * 2)()
+        for i, owner in enumerate((self.data, self.noise_source)):
+            parts[i].src, parts[i].dst, parts[i].bytes = owner.counter_ptr(), steps[0, i:].data_ptr(), 8
+        _capi.check(lib.iaf_state_snapshot(parts, 2, _ptr(steps[1]), _stream()))     # (read in the stream: no tell(), which synchronises)
+        try:
+            m.prepare_weights()
+        except _recover.SWITCHED:         # an object reports an EARLIER launch and has switched kernels: run() captures again
+            self._graphs = self._kept = None
+            m.prepare_weights()
+        x = self.data.next_batch(B)
+        x_mean = m.forward(x, m.draw_noise(B, self.noise_source, which="posterior"))[0]
+        x_gen = m.sample(B, self.noise_source, temperature=temperature)
+        rec8, recf, rr = image_grid([(x, half), (x_mean, half)], total)
+        smp8, smpf, sr = image_grid([(x_gen, B, total)], total)
+        host = torch.cat([rec8.reshape(-1), smp8.reshape(-1), steps[0].view(torch.uint8),
+                          torch.cat([rr, sr])[:, 2].contiguous().view(torch.uint8)]).cpu()      # the one synchronisation
+        n8 = rec8.numel()
+        data_step, noise_step = (int(v) & (1 << 64) - 1 for v in host[2 * n8:2 * n8 + 16].clone().view(torch.int64))
+        nonfinite = int(host[2 * n8 + 16:].clone().view(torch.int32).to(torch.int64).sum())
+        if nonfinite > 0:
+            warnings.warn("EvalPass.images: %d non-finite element(s) in what the pictures show: the slots concerned hold NaN / 0" % nonfinite,
+                          RuntimeWarning, stacklevel=2)
+        return {"reconstructions": host[:n8].reshape(rec8.shape).numpy(), "samples": host[n8:2 * n8].reshape(smp8.shape).numpy(),
+                "reconstructions_f32": recf, "samples_f32": smpf, "inputs": x[:half], "x_mean": x_mean[:half], "x_gen": x_gen,
+                "data_step": data_step, "noise_step": noise_step, "nonfinite": nonfinite}
 
     @property
     def graphed(self):

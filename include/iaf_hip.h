@@ -888,6 +888,54 @@ int iaf_rng_step_ptr(iaf_rng_t* r, const uint64_t** step);
 int iaf_data_step_ptr(iaf_data_t* d, const uint64_t** step);
 int iaf_skip_counter_ptr(const iaf_skip_counter_t* c, const unsigned** count);
 
+/* ------------------------------------------------------------------------------------------
+ * run_eval's image summaries (tf_train.py:329-376): img_stretch and img_tile (tf_utils/common.py:118-168) on the device, for images
+ * that are already there.  iaf_amd/images.py and EvalPass.images() build the reference's two pictures from these two calls.
+ *
+ * iaf_img_range: ONE launch that leaves the range of src[0..n_elems) (dtype IAF_IMG_U8 or IAF_IMG_F32) in `record`, 16 bytes of device
+ *   memory, 8-byte aligned:   float lo; float hi; uint32 nonfinite; uint32 arrivals.
+ *   lo / hi: the minimum / maximum of the elements, as fp32; nonfinite: the number of NaN or +-inf elements, which are left OUT of lo
+ *   and hi (all of them non-finite: lo = +inf, hi = -inf); a zero of either sign is reported as +0.  Min, max and a count do not depend
+ *   on the order they are taken in: the record is exact and the same bits on every run.
+ *   16-byte loads over the aligned body behind a scalar head up to src's first 16-byte boundary, and a scalar tail; a wave's 64 lanes
+ *   combine by shuffles, the workgroup's waves through LDS.  Up to 16 KiB one workgroup; beyond that one more per 16 KiB (at most 256),
+ *   which combine in the record itself with agent-scope atomics: `arrivals` counts them, and the last one to arrive sets it back to 0.
+ *   `arrivals` must be 0 before the first call on a record (zero the 16 bytes once); after that a record is reused, and a replayed
+ *   graph needs no memset between replays.  One record is written by one launch at a time.
+ *   Errors, before any device work: IAF_ERR_NULL (src, record); IAF_ERR_SHAPE (unknown dtype, n_elems = 0); IAF_ERR_WORKSPACE (record
+ *   not 8-byte aligned, an fp32 src not 4-byte aligned).
+ *
+ * iaf_img_grid: ONE launch that writes EVERY element of the grid(s) -- image pixels, borders, empty tiles; the caller clears nothing.
+ *   The grid of n_imgs tiles of H x W pixels (img_tile at aspect_ratio 1.0), in fp64:
+ *       ar = W / H;   th = ceil(sqrt(n_imgs * ar));   tw = ceil(sqrt(n_imgs / ar));
+ *       Hg = (H + border) * th - border;   Wg = (W + border) * tw - border;     grids are [Hg, Wg, C] (HWC), C = 1 or 3.
+ *   Slot s < n_imgs sits at tile (s / tw, s % tw) and shows image s / n_src of source s % n_src (n_src = 1 or 2; sources are NCHW
+ *   [*, C, H, W], uint8 or fp32, with at least ceil(n_imgs / n_src) images).  Border pixels and empty tiles hold border_color.
+ *   The stretch of a source, all fp32 unless marked, from its `outer` record (lo_o, hi_o):
+ *       d_o = fp32(fp64(fp32(hi_o - lo_o)) + 1e-12);      s1(v) = (v - lo_o) / d_o          -- img_stretch over the record's slice
+ *   and, when `inner` is given (lo_i, hi_i; the range of a slice that lies WITHIN the outer one):
+ *       a = s1(lo_i);   b = s1(hi_i) - a;   d_i = fp32(fp64(b) + 1e-12);   s2(v) = (s1(v) - a) / d_i
+ *   s1 is monotone (a subtraction of and a division by constants, each rounded monotonically), so the minimum and the maximum of s1 over
+ *   the inner slice are s1 of that slice's minimum and maximum: s2 IS the reference's second img_stretch (run_eval stretches the samples
+ *   over the whole batch, then over the ones it shows), with no second reduction over stretched data.  The divisions are IEEE.
+ *   A source one of whose records in use has nonfinite > 0 shows NaN in grid_f32 and 0 in grid_u8 in all its slots (NumPy would give a
+ *   mixture of NaN and inf); the other source, the borders and the empty tiles are not affected.
+ *   grid_u8 = (uint8) min(max(floor((double) v * 255.0 + 0.5), 0), 255), NaN -> 0, for every element v of grid_f32, border_color
+ *   included.  Product and sum are exact in fp64 for an fp32 v, so the byte does not depend on FMA contraction and is a function of
+ *   grid_f32's bits.  This rule is OURS: how TensorFlow's image summary quantises is not in the reference's tree.
+ *   Either grid may be NULL, not both.  The source table is read during the call and travels in the kernel arguments: no upload, no
+ *   host synchronisation, capturable (one kernel node).
+ *   Errors, before any device work: IAF_ERR_NULL (table, both grids, a source's ptr or outer); IAF_ERR_SHAPE (n_src outside 1..2,
+ *   n_imgs < 1, C not 1 or 3, H or W < 1, border < 0, unknown dtype, a grid of 2^31 pixels or more); IAF_ERR_WORKSPACE (a record not
+ *   8-byte aligned, an fp32 source or grid_f32 not 4-byte aligned).
+ * ------------------------------------------------------------------------------------------ */
+#define IAF_IMG_U8 0
+#define IAF_IMG_F32 1
+typedef struct { const void* ptr; int dtype; const void* outer; const void* inner; /* may be NULL */ } iaf_img_source_t;
+int iaf_img_range(const void* src, int dtype, size_t n_elems, void* record /* device, 16 bytes */, void* stream);
+int iaf_img_grid(const iaf_img_source_t* sources, int n_src, int n_imgs, int C, int H, int W, int border, float border_color,
+                 float* grid_f32 /* device [Hg,Wg,C], may be NULL */, unsigned char* grid_u8 /* likewise */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
