@@ -54,6 +54,8 @@ def _units():
     units = [(os.path.join(CSRC, "iaf_engine.hip"), os.path.join(OBJDIR, "iaf_engine.o"), []),
              # the entry points that take no stack and no conv: optimiser, guard, summaries, noise source, dataset, state snapshot
              (os.path.join(CSRC, "iaf_train_services.hip"), os.path.join(OBJDIR, "iaf_train_services.o"), []),
+             # ... and the model's own: its two ends around the layer stack, the objective side, the elementwise pieces of the init pass
+             (os.path.join(CSRC, "iaf_model_ops.hip"), os.path.join(OBJDIR, "iaf_model_ops.o"), []),
              # host-only: the RCCL gradient exchange (librccl is dlopen'ed at run time, no link dependency)
              (os.path.join(CSRC, "iaf_comm.cpp"), os.path.join(OBJDIR, "iaf_comm.o"), ["-x", "hip"]),
              # the weight gradient on the bf16 matrix cores (transposing LDS reads)

@@ -1,8 +1,14 @@
-// iaf_common.hpp -- what more than one translation unit of the engine uses (iaf_engine.hip, iaf_train_services.hip): the grid of the
-// elementwise launches and two device helpers of the reductions.  No __global__ function lives here: a kernel header is included by
-// exactly one unit (the kernels are not static, a second inclusion is a duplicate symbol at link time).
+// iaf_common.hpp -- what more than one translation unit of the engine uses (iaf_engine.hip, iaf_model_ops.hip, iaf_train_services.hip):
+// the grid of the elementwise launches, HIP_TRY and two device helpers of the reductions.  No __global__ function lives here: a kernel
+// header is included by exactly one unit (the kernels are not static, a second inclusion is a duplicate symbol at link time).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#define HIP_TRY(expr)                               \
+    do {                                            \
+        hipError_t _e = (expr);                     \
+        if (_e != hipSuccess) return (int)_e;       \
+    } while (0)
 
 static dim3 ew_grid(size_t n) {
     size_t g = (n + 255) / 256;

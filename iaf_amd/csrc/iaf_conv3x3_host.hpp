@@ -1,5 +1,5 @@
-// iaf_conv3x3_host.hpp -- host side + C ABI of the plain / single masked 3x3 convs (iaf_conv3x3_*), data-dependent init and the likelihood.
-// Part of the single translation unit iaf_engine.hip (included there, in order; not a standalone header).
+// iaf_conv3x3_host.hpp -- host side + C ABI of the plain / single masked 3x3 convs (iaf_conv3x3_*): functions of an iaf_conv3x3_t or a batch of them.
+// A section of iaf_engine.hip (included there last: it uses the stack's launch logic; not a standalone header).
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
@@ -186,62 +186,6 @@ extern "C" int iaf_conv3x3_prepare_deconv(iaf_conv3x3_t* c, const float* V, cons
     c->prepared = true;
     c->deconv = true;
     return IAF_OK;
-}
-
-// 2x resampling of an NCHW tensor (modes: IAF_RESAMPLE_* in include/iaf_hip.h); H, W = size of the SMALLER tensor
-extern "C" int iaf_resample2(const float* src, float* dst, int B, int C, int H, int W, int mode, void* stream) {
-    if (!src || !dst) return IAF_ERR_NULL;
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || mode < 0 || mode > 5) return IAF_ERR_SHAPE;
-    const bool down = (mode == IAF_RESAMPLE_DOWN_EVEN || mode == IAF_RESAMPLE_DOWN_ODD || mode == IAF_RESAMPLE_DOWN_SUM4);
-    const size_t n_dst = (size_t)B * C * H * W * (down ? 1 : 4);
-    hipLaunchKernelGGL(iaf_resample2_kernel, ew_grid(n_dst), dim3(256), 0, (hipStream_t)stream, src, dst, n_dst, H, W, mode);
-    return (int)hipGetLastError();
-}
-
-// eps' with (qm+rm) + exp(ql+rl) * eps' == z: the posterior noise that reproduces a given sample z (mode "init" of
-// IAFLayer.down runs the posterior block on a PRIOR sample, tf_train.py:60-61,67-85)
-__global__ __launch_bounds__(256) void iaf_noise_from_sample_kernel(const float* __restrict__ z, const float* __restrict__ qm,
-                                                                   const float* __restrict__ ql, const float* __restrict__ rm,
-                                                                   const float* __restrict__ rl, float* __restrict__ eps, size_t n) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        eps[i] = (z[i] - (qm[i] + rm[i])) * __expf(-(ql[i] + rl[i]));
-}
-extern "C" int iaf_noise_from_sample(const float* z, const float* qz_mean, const float* qz_logsd, const float* rz_mean,
-                                     const float* rz_logsd, float* eps_out, size_t n, void* stream) {
-    if (!z || !qz_mean || !qz_logsd || !rz_mean || !rz_logsd || !eps_out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_noise_from_sample_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, z, qz_mean, qz_logsd, rz_mean,
-                       rz_logsd, eps_out, n);
-    return (int)hipGetLastError();
-}
-
-// kl = logq0 + logdet - logp: models.py:175,298,328 when the three terms come from separate launches (posterior
-// 'up_iaf2_nl': the IAF step runs in the up pass, the prior is only known in the down pass)
-__global__ __launch_bounds__(256) void iaf_kl_combine_kernel(const float* __restrict__ logq0, const float* __restrict__ logdet,
-                                                            const float* __restrict__ logp, float* __restrict__ kl, size_t n) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) kl[i] = (logq0[i] + logdet[i]) - logp[i];
-}
-extern "C" int iaf_kl_combine(const float* logq0, const float* logdet, const float* logp, float* kl, size_t n, void* stream) {
-    if (!logq0 || !logdet || !logp || !kl) return IAF_ERR_NULL;
-    if (n == 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_kl_combine_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, logq0, logdet, logp, kl, n);
-    return (int)hipGetLastError();
-}
-
-// out[j] = sum_i mat[i][j]: the per-row KL costs of all layers of a model -> sum_kl_costs (tf_train.py:198-200:
-// `kl_cost += cur_cost` over the layer loop), the second argument of compute_lowerbound
-__global__ __launch_bounds__(256) void iaf_colsum_kernel(const float* __restrict__ mat, float* __restrict__ out, int m, int n) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    out[j] = iaf_col_sum(mat, m, n, j);            // (iaf_kernels_misc.hpp: shared with iaf_eval_tail_kernel)
-}
-extern "C" int iaf_colsum(const float* mat, float* out, int m, int n, void* stream) {
-    if (!mat || !out) return IAF_ERR_NULL;
-    if (m <= 0 || n <= 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_colsum_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, mat, out, m, n);
-    return (int)hipGetLastError();
 }
 
 // weight prep of many plain convs in one launch (the four convs of every IAFLayer of a model): descriptors in device
@@ -819,23 +763,6 @@ extern "C" int iaf_conv3x3_work(const iaf_conv3x3_t* c, int B, int H, int W, dou
     // input + output activations once, raw V/g/b once
     if (bytes) *bytes = 4.0 * (P * (c->n_in + c->n_out) + 9.0 * c->n_in * c->n_out + 2.0 * c->n_out);
     return IAF_OK;
-}
-
-extern "C" int iaf_datainit_normalize(const float* x_init, const float* add, float* y, float* g, float* b, int B, int C,
-                                      int HW, float init_scale, void* stream) {
-    if (!x_init || !g || !b) return IAF_ERR_NULL;
-    if (B <= 0 || C <= 0 || HW <= 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_datainit_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, x_init, add, y, g, b, B, C, HW, init_scale);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_discretized_logistic(const float* mean, const float* logscale, int logscale_is_scalar, const float* sample,
-                                        float* out, int B, size_t n_per_row, float binsize, void* stream) {
-    if (!mean || !logscale || !sample || !out) return IAF_ERR_NULL;
-    if (B <= 0 || n_per_row == 0 || !(binsize > 0.f)) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_disc_logistic_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, mean, logscale,
-                       logscale_is_scalar ? 1 : 0, sample, out, n_per_row, binsize);
-    return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -28,15 +28,17 @@
 // unit: its __global__ functions are not static):
 //   iaf_conv_kernel.hpp       the implicit-GEMM conv kernel template (instantiated per launch shape in iaf_conv_inst.hip)
 //   iaf_kernels_prep.hpp      mask / weight-norm / repack kernels
-//   iaf_common.hpp            shared with iaf_train_services.hip: the elementwise launch grid, two device helpers of the reductions
-//   iaf_kernels_misc.hpp      KL + free bits, Gaussian, lower bound, evaluation tail, data-dependent init, likelihood
+//   iaf_common.hpp            shared with the two units below: the elementwise launch grid, HIP_TRY, two device helpers of the reductions
+//   iaf_kernels_misc.hpp      what the stack itself launches: KL + free bits, max-diff, the inverse step's control kernels
 //   iaf_kernels_backward.hpp  weight gradient, weight-norm backward, staging, posterior-block backward pieces
 //   iaf_kernels_generic.hpp   direct-conv fallback for channel counts outside the MFMA path
-//   iaf_kernels_resample.hpp  2x resampling and the deconv2d weight prep (downsampling IAFLayer)
-//   (this file)               stack object, launch logic, C ABI of the masked stack, forward / inverse / training
-//   iaf_conv3x3_host.hpp      C ABI of the plain and single masked 3x3 convs, init, likelihood
-//   iaf_model_edge.hpp        the two ends of the model around the layer stack (CVAE1._forward: x_enc, h_top, x_dec, obj / loss)
-// A unit of its own, with the entry points that take no stack and no conv:
+//   iaf_kernels_resample.hpp  the deconv2d weight prep and its backward (downsampling IAFLayer)
+//   (this file)               stack object, launch logic, C ABI of the masked stack, forward / inverse / training, free bits
+//   iaf_conv3x3_host.hpp      C ABI of the plain and single masked 3x3 convs
+// Units of their own, with the entry points that take no stack and no conv:
+//   iaf_model_ops.hip         the model's own operations: its two ends around the layer stack (CVAE1._forward: x_enc, h_top, x_dec,
+//                             obj / loss) and their backward (iaf_kernels_edge.hpp); Gaussian sample / logps, 'up_iaf2_nl' backward halves,
+//                             lower bound, evaluation tail, data-dependent init, likelihood, 2x resampling (iaf_kernels_objective.hpp)
 //   iaf_train_services.hip    Adamax + EMA, skip counter, guard scans, summaries (iaf_kernels_train.hpp), the device noise source
 //                             (iaf_kernels_rng.hpp), the device-resident dataset and the state snapshot (iaf_kernels_data.hpp)
 #include <hip/hip_runtime.h>
@@ -183,12 +185,6 @@ struct iaf_stack : PackState {     // precision (forward convs: F32 = the exact 
     hipEvent_t* prof_start = nullptr;
     hipEvent_t* prof_stop = nullptr;
 };
-
-#define HIP_TRY(expr)                               \
-    do {                                            \
-        hipError_t _e = (expr);                     \
-        if (_e != hipSuccess) return (int)_e;       \
-    } while (0)
 
 // ---- descriptor table of a batched prep launch: host-built PrepLayer array -> device ---------------------------------
 // (the ring of pinned snapshots had no completion tracking.)  An async upload reads its pinned source when the
@@ -1946,7 +1942,8 @@ extern "C" int iaf_posterior_block_forward(iaf_stack_t* s, const float* qz_mean,
 }
 
 // free bits on given KL elements (tf_train.py:77-85; models.py:455-466): kl_elem [B,C,H,W] -> kl_obj [B], kl_cost [B];
-// scratch: B*C floats
+// scratch: B*C floats.  (These three take no stack, yet stay in this unit, not iaf_model_ops.hip: they launch the two kernels of the
+// posterior block above and of launch_kl_from_parts, and a kernel is launched only from the unit that defines it.)
 static int kl_free_bits_impl(const float* kl_elem, float* kl_obj, float* kl_cost, float* gate, int B, int C, int HW, float kl_min,
                              float* scratch, void* stream, int groups = 1) {
     if (!kl_elem || !kl_obj || !kl_cost || !scratch) return IAF_ERR_NULL;
@@ -1972,134 +1969,6 @@ extern "C" int iaf_kl_free_bits_gate(const float* kl_elem, float* kl_obj, float*
 extern "C" int iaf_kl_free_bits_grouped(const float* kl_elem, float* kl_obj, float* kl_cost, float* gate_or_null, int B, int C, int HW,
                                         int groups, float kl_min, float* scratch, void* stream) {
     return kl_free_bits_impl(kl_elem, kl_obj, kl_cost, gate_or_null, B, C, HW, kl_min, scratch, stream, groups);
-}
-
-extern "C" int iaf_gaussian_sample(const float* mean, const float* logvar, const float* noise, float* out, size_t n,
-                                   void* stream) {
-    if (!mean || !logvar || !noise || !out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_OK;
-    hipLaunchKernelGGL(iaf_gauss_sample_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, mean, logvar, noise, out, n, 1.0f);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_gaussian_sample_logsd(const float* mean, const float* logsd, const float* noise, float* out, size_t n,
-                                         void* stream) {
-    if (!mean || !logsd || !noise || !out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_OK;
-    hipLaunchKernelGGL(iaf_gauss_sample_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, mean, logsd, noise, out, n, 2.0f);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_gaussian_logps(const float* mean, const float* logvar, const float* sample, float* out, size_t n,
-                                  void* stream) {
-    if (!mean || !logvar || !sample || !out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_OK;
-    hipLaunchKernelGGL(iaf_gauss_logps_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, mean, logvar, sample, out, n, 1.0f);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_gaussian_logps_logsd(const float* mean, const float* logsd, const float* sample, float* out, size_t n,
-                                        void* stream) {
-    if (!mean || !logsd || !sample || !out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_OK;
-    hipLaunchKernelGGL(iaf_gauss_logps_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, mean, logsd, sample, out, n, 2.0f);
-    return (int)hipGetLastError();
-}
-
-// The elementwise halves of the backward of models.cvae_layer 'up_iaf2_nl' around iaf_step_backward (iaf_kernels_misc.hpp:
-// UpIafBwdP).  gate [n_z] non-NULL: free bits, G = gate[c] * gscale; else G = dko[b].
-extern "C" int iaf_up_iaf2_backward_pre(const float* z, const float* pz_mean, const float* pz_logsd, const float* d_h, const float* d_up,
-                                        const float* gate, float gscale, const float* dko, float* dz_tot, float* G, float* d_down_conv1,
-                                        int B, int n_h, int n_z, int HW, void* stream) {
-    if (!z || !pz_mean || !pz_logsd || !d_h || !dz_tot || !G || !d_down_conv1 || (!gate && !dko)) return IAF_ERR_NULL;
-    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
-    UpIafBwdP p;
-    memset(&p, 0, sizeof(p));
-    p.z = z; p.pz_mean = pz_mean; p.pz_logsd = pz_logsd; p.d_h = d_h; p.d_up = d_up; p.gate = gate; p.dko = dko; p.gscale = gscale;
-    p.dz_tot = dz_tot; p.Gf = G; p.d_dc1 = d_down_conv1; p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
-    hipLaunchKernelGGL(iaf_up_iaf2_bwd_pre_kernel, ew_grid((size_t)B * (n_h + 2 * n_z) * HW), dim3(256), 0, (hipStream_t)stream, p);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_up_iaf2_backward_post(const float* dz0, const float* z0, const float* qz_mean, const float* G, const float* dctx,
-                                         const float* d_up, float* d_up_conv1, int B, int n_h, int n_z, int HW, void* stream) {
-    if (!dz0 || !z0 || !qz_mean || !G || !dctx || !d_up_conv1) return IAF_ERR_NULL;
-    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
-    UpIafBwdP p;
-    memset(&p, 0, sizeof(p));
-    p.dz0 = dz0; p.z0 = z0; p.qz_mean = qz_mean; p.Gf = const_cast<float*>(G); p.dctx = dctx; p.d_up = d_up; p.d_uc1 = d_up_conv1;
-    p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
-    hipLaunchKernelGGL(iaf_up_iaf2_bwd_post_kernel, ew_grid((size_t)B * (2 * n_h + 2 * n_z) * HW), dim3(256), 0, (hipStream_t)stream, p);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_lowerbound_stream_init(float* run_max, float* run_sum, int n, void* stream) {
-    if (!run_max || !run_sum) return IAF_ERR_NULL;
-    if (n <= 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_lb_init_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, run_max, run_sum, n);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_lowerbound_stream_update(float* run_max, float* run_sum, const float* log_pxz, const float* sum_kl,
-                                            int n, int k_chunk, void* stream) {
-    if (!run_max || !run_sum || !log_pxz || !sum_kl) return IAF_ERR_NULL;
-    if (n <= 0 || k_chunk <= 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_lb_update_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, run_max, run_sum,
-                       log_pxz, sum_kl, n, k_chunk);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_lowerbound_stream_finalize(const float* run_max, const float* run_sum, float* out, int n,
-                                              int k_total, void* stream) {
-    if (!run_max || !run_sum || !out) return IAF_ERR_NULL;
-    if (n <= 0 || k_total <= 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_lb_finalize_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, run_max, run_sum,
-                       out, n, k_total);
-    return (int)hipGetLastError();
-}
-
-// the tail of an evaluation pass and the epoch's record (iaf_kernels_misc.hpp: iaf_eval_tail_kernel): one workgroup per batch row
-static_assert(sizeof(EvalRec) == 32, "the evaluation record is 32 bytes (include/iaf_hip.h)");
-extern "C" int iaf_eval_reset(void* record, float* run_max, float* run_sum, int n, void* stream) {
-    if (!record || !run_max || !run_sum) return IAF_ERR_NULL;
-    if (n < 1 || n > 65535) return IAF_ERR_SHAPE;
-    if (((uintptr_t)record & 7) != 0) return IAF_ERR_WORKSPACE;
-    hipLaunchKernelGGL(iaf_eval_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (EvalRec*)record, run_max,
-                       run_sum, n);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_eval_tail(const float* x_out, const float* dec_log_stdv, const float* x, size_t n_per_row, float binsize,
-                             const float* layer_cost, int n_layers, int n, float* run_max, float* run_sum, int k,
-                             const long long* indices, float* per_image, float* bound, void* record, void* stream) {
-    if (!x_out || !dec_log_stdv || !x || !layer_cost || !run_max || !run_sum || !bound || !record) return IAF_ERR_NULL;
-    if (per_image && !indices) return IAF_ERR_NULL;
-    if (n < 1 || n > 65535 || n_layers < 1 || k < 1 || n_per_row == 0 || !(binsize > 0.f)) return IAF_ERR_SHAPE;
-    if (((uintptr_t)record & 7) != 0) return IAF_ERR_WORKSPACE;
-    hipLaunchKernelGGL(iaf_eval_tail_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, x_out, dec_log_stdv, x, n_per_row, binsize,
-                       layer_cost, n_layers, n, run_max, run_sum, k, indices, per_image, bound, (EvalRec*)record);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_compute_lowerbound(const float* log_pxz, const float* sum_kl, float* out, int n, int k, void* stream) {
-    if (!log_pxz || !sum_kl || !out) return IAF_ERR_NULL;
-    if (n <= 0 || k <= 0) return IAF_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (k == 1) {
-        hipLaunchKernelGGL(iaf_lb_k1_kernel, dim3((n + 255) / 256), dim3(256), 0, st, log_pxz, sum_kl, out, n);
-        return (int)hipGetLastError();
-    }
-    // single-chunk streaming pass with the state kept in `out` itself is not possible (two words
-    // per image); k>1 callers provide state through the stream API.  For convenience allocate on
-    // the stream-ordered pool.
-    float* state = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&state, 2 * (size_t)n * sizeof(float), st));
-    hipLaunchKernelGGL(iaf_lb_init_kernel, dim3((n + 255) / 256), dim3(256), 0, st, state, state + n, n);
-    hipLaunchKernelGGL(iaf_lb_update_kernel, dim3((n + 3) / 4), dim3(256), 0, st, state, state + n, log_pxz, sum_kl, n, k);
-    hipLaunchKernelGGL(iaf_lb_finalize_kernel, dim3((n + 255) / 256), dim3(256), 0, st, state, state + n, out, n, k);
-    int rc = (int)hipGetLastError();
-    HIP_TRY(hipFreeAsync(state, st));
-    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2750,4 +2619,3 @@ extern "C" int iaf_step_work(const iaf_stack_t* s, int B, int H, int W, double* 
 }
 
 #include "iaf_conv3x3_host.hpp"
-#include "iaf_model_edge.hpp"

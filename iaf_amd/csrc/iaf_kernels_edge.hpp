@@ -1,11 +1,12 @@
-// iaf_model_edge.hpp -- the two ends of the model around the IAFLayer stack, CVAE1._forward (tf_train.py:150-218): the image
+// iaf_kernels_edge.hpp -- kernels of the two ends of the model around the IAFLayer stack, CVAE1._forward (tf_train.py:150-218): the image
 // scaling (:153-154, 159), conv2d("x_enc", x, h_size, [5,5], [2,2]) (:183), the tiled h_top (:189-192), deconv2d("x_dec", elu(h), 3,
 // [5,5]) + clip (:206-208) and the two scalar sums obj / loss (:211, 218).  Tiny channel counts on one side (3 image channels): not
 // MFMA work -- direct convolutions (a few output channels per thread; the deconv by output phases with its input channels
 // split over 16 thread slices), latency-bound, 10-20 microseconds each at the BASELINE batch.
-// Part of the single translation unit iaf_engine.hip (included there; not a standalone header).
+// Then their backward, and the elementwise pieces of the data-dependent init pass.
+// Included by iaf_model_ops.hip and by no other unit; the C ABI over these kernels is there.
 #pragma once
-#include "iaf_conv_epilogue.hpp"     // fast_divmod
+#include "iaf_conv_kernel.hpp"       // elu_f, f32x4
 
 // out[(b k + s)][i] = clip((x[b][i] + 0.5) / 256, 0, 1) - 0.5  for s < k   (tf_train.py:153-154, repeat :159)
 __global__ __launch_bounds__(256) void iaf_image_to_float_kernel(const unsigned char* __restrict__ x, float* __restrict__ out,
@@ -197,87 +198,6 @@ __global__ __launch_bounds__(256) void iaf_sum_axpy_kernel(const float* __restri
     if (threadIdx.x == 0) out[0] = red[0];
 }
 
-// ---- C ABI -------------------------------------------------------------------------------------------------------------------
-extern "C" int iaf_image_to_float(const unsigned char* x, float* out, int B, size_t n_per_image, int k, void* stream) {
-    if (!x || !out) return IAF_ERR_NULL;
-    if (B <= 0 || k <= 0 || n_per_image == 0) return IAF_ERR_SHAPE;
-    const size_t total = (size_t)B * k * n_per_image;
-    hipLaunchKernelGGL(iaf_image_to_float_kernel, ew_grid(total), dim3(256), 0, (hipStream_t)stream, x, out, n_per_image, total, k);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_convk_weightnorm(const float* V, const float* g, float* w, int kh, int kw, int n_in, int n_out, int deconv,
-                                    void* stream) {
-    if (!V || !g || !w) return IAF_ERR_NULL;
-    if (kh <= 0 || kw <= 0 || n_in <= 0 || n_out <= 0) return IAF_ERR_SHAPE;
-    // conv: V [kh,kw,n_in,n_out] -> one workgroup per n_out; deconv: V [kh,kw,n_out,n_in] -> one per n_in
-    hipLaunchKernelGGL(iaf_convk_weightnorm_kernel, dim3(deconv ? n_in : n_out), dim3(256), 0, (hipStream_t)stream, V, g, w, kh * kw,
-                       deconv ? n_out : n_in, deconv ? n_in : n_out, deconv ? 1 : 0);
-    return (int)hipGetLastError();
-}
-
-// TF "SAME": out = ceil(n / s), total padding max((out - 1) s + k - n, 0), the smaller half first
-static void same_pad(int n, int k, int s, int* out, int* before) {
-    *out = (n + s - 1) / s;
-    int tot = (*out - 1) * s + k - n;
-    if (tot < 0) tot = 0;
-    *before = tot / 2;
-}
-
-extern "C" int iaf_convk_forward(const float* x, const float* w, const float* b, float* y, int B, int n_in, int H, int W, int n_out,
-                                 int kh, int kw, int stride, int elu_input, void* stream) {
-    if (!x || !w || !b || !y) return IAF_ERR_NULL;
-    if (B <= 0 || n_in <= 0 || n_out <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || stride <= 0) return IAF_ERR_SHAPE;
-    ConvKP p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.b = b; p.y = y; p.B = B; p.n_in = n_in; p.H = H; p.W = W; p.n_out = n_out; p.kh = kh; p.kw = kw;
-    p.stride = stride; p.elu = elu_input ? 1 : 0;
-    same_pad(H, kh, stride, &p.OH, &p.pad_t);
-    same_pad(W, kw, stride, &p.OW, &p.pad_l);
-    const size_t npx = (size_t)B * p.OH * p.OW;
-    if (npx > (1u << 30)) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_convk_forward_kernel, dim3((unsigned)((npx + 255) / 256), (n_out + CK_NO - 1) / CK_NO), dim3(256), 0,
-                       (hipStream_t)stream, p);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_deconvk_forward(const float* x, const float* w, const float* b, float* y, int B, int n_in, int H, int W, int n_out,
-                                   int kh, int kw, int stride, int elu_input, float clip_lo, float clip_hi, void* stream) {
-    if (!x || !w || !b || !y) return IAF_ERR_NULL;
-    if (B <= 0 || n_in <= 0 || n_out <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || stride <= 0) return IAF_ERR_SHAPE;
-    ConvKP p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.b = b; p.y = y; p.B = B; p.n_in = n_in; p.H = H; p.W = W; p.n_out = n_out; p.kh = kh; p.kw = kw;
-    p.stride = stride; p.elu = elu_input ? 1 : 0; p.clip_lo = clip_lo; p.clip_hi = clip_hi;
-    p.OH = H * stride; p.OW = W * stride;
-    int o;
-    same_pad(p.OH, kh, stride, &o, &p.pad_t);       // the forward conv this transposes maps [OH, OW] -> [H, W]
-    same_pad(p.OW, kw, stride, &o, &p.pad_l);
-    const size_t npx = (size_t)B * H * W;
-    if (npx > (1u << 30) || stride > 8) return IAF_ERR_SHAPE;
-    // dynamic LDS: the weights of one output phase, at most ceil(kh/s) ceil(kw/s) taps x DK_NO channels x n_in
-    const size_t wl_bytes = (size_t)((kh + stride - 1) / stride) * ((kw + stride - 1) / stride) * DK_NO * n_in * sizeof(float);
-    if (wl_bytes > 60 * 1024) return IAF_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(iaf_deconvk_forward_kernel, dim3((unsigned)((npx + 15) / 16), stride * stride, (n_out + DK_NO - 1) / DK_NO),
-                       dim3(256), wl_bytes, (hipStream_t)stream, p);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_tile_channels(const float* v, float* out, int B, int C, int HW, void* stream) {
-    if (!v || !out) return IAF_ERR_NULL;
-    if (B <= 0 || C <= 0 || HW <= 0) return IAF_ERR_SHAPE;
-    const size_t total = (size_t)B * C * HW;
-    hipLaunchKernelGGL(iaf_tile_channels_kernel, ew_grid(total), dim3(256), 0, (hipStream_t)stream, v, out, total, C, HW);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_sum_axpy(const float* a, const float* b, float sb, float* out, int n, void* stream) {
-    if (!a || !out) return IAF_ERR_NULL;
-    if (n <= 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_sum_axpy_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, b, sb, out, n);
-    return (int)hipGetLastError();
-}
-
 // ==================================================================================================================================
 // Backward of the two ends: what TF autodiff derives for tf_train.py:183, 189-192, 206-211 in `opt.compute_gradients(obj)` (:128)
 // ==================================================================================================================================
@@ -438,57 +358,6 @@ __global__ __launch_bounds__(256) void iaf_mul_elu_grad_kernel(const float* __re
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = g[i] * (h[i] > 0.f ? 1.0f : __expf(h[i]));
 }
 
-extern "C" int iaf_discretized_logistic_backward(const float* mean, const float* logscale, const float* sample, float up, float clip_lo,
-                                                 float clip_hi, float* d_mean, float* d_logscale_rows, int B, size_t n_per_row,
-                                                 float binsize, void* stream) {
-    if (!mean || !logscale || !sample || !d_mean || !d_logscale_rows) return IAF_ERR_NULL;
-    if (B <= 0 || n_per_row == 0 || !(binsize > 0.f)) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_discretized_logistic_bwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, mean, logscale, sample, up, clip_lo,
-                       clip_hi, d_mean, d_logscale_rows, n_per_row, binsize);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_convk_wgrad(const float* x, const float* dy, float* dW, int B, int n_small, int H, int W, int n_big, int kh, int kw,
-                               int stride, int elu_x, int elu_dy, void* stream) {
-    if (!x || !dy || !dW) return IAF_ERR_NULL;
-    if (B <= 0 || n_small <= 0 || n_big <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || stride <= 0) return IAF_ERR_SHAPE;
-    ConvKWP p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.dy = dy; p.dW = dW; p.B = B; p.n_small = n_small; p.H = H; p.W = W; p.n_big = n_big; p.kh = kh; p.kw = kw;
-    p.stride = stride; p.elu_x = elu_x ? 1 : 0; p.elu_dy = elu_dy ? 1 : 0;
-    same_pad(H, kh, stride, &p.OH, &p.pad_t);
-    same_pad(W, kw, stride, &p.OW, &p.pad_l);
-    if ((long long)B * p.OH * p.OW > (1LL << 24)) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_convk_wgrad_kernel, dim3(kh * kw * n_small, (n_big + 15) / 16), dim3(256), 0, (hipStream_t)stream, p);
-    return (int)hipGetLastError();
-}
-
-// dV (V's layout), dg [n_out]; deconv: scratch = n_in * n_out floats
-extern "C" int iaf_convk_weightnorm_backward(const float* V, const float* g, const float* dW, float* dV, float* dg, float* scratch,
-                                             int kh, int kw, int n_in, int n_out, int deconv, void* stream) {
-    if (!V || !g || !dW || !dV || !dg || (deconv && !scratch)) return IAF_ERR_NULL;
-    if (kh <= 0 || kw <= 0 || n_in <= 0 || n_out <= 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_convk_weightnorm_bwd_kernel, dim3(deconv ? n_in : n_out), dim3(256), 0, (hipStream_t)stream, V, g, dW, dV,
-                       deconv ? scratch : dg, kh * kw, deconv ? n_out : n_in, deconv ? n_in : n_out, deconv ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    if (deconv) return iaf_colsum(scratch, dg, n_in, n_out, stream);
-    return IAF_OK;
-}
-
-extern "C" int iaf_channel_sum(const float* x, float* out, int B, int C, int HW, void* stream) {
-    if (!x || !out) return IAF_ERR_NULL;
-    if (B <= 0 || C <= 0 || HW <= 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_channel_sum_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, x, out, B, C, HW);
-    return (int)hipGetLastError();
-}
-
-extern "C" int iaf_mul_elu_grad(const float* g, const float* h, float* out, size_t n, void* stream) {
-    if (!g || !h || !out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_mul_elu_grad_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, g, h, out, n);
-    return (int)hipGetLastError();
-}
-
 // ---- elementwise pieces of the data-dependent init pass (mode "init", tf_train.py:60-61, 70-71, 94, 208) -----------------------------
 __global__ __launch_bounds__(256) void iaf_axpby_kernel(const float* __restrict__ a, float sa, const float* __restrict__ b, float sb,
                                                        float* __restrict__ out, size_t n) {
@@ -504,22 +373,4 @@ __global__ __launch_bounds__(256) void iaf_affine_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void iaf_clip_kernel(const float* __restrict__ x, float lo, float hi, float* __restrict__ out, size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = fminf(fmaxf(x[i], lo), hi);
-}
-extern "C" int iaf_axpby(const float* a, float sa, const float* b, float sb, float* out, size_t n, void* stream) {
-    if (!a || !b || !out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_axpby_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, a, sa, b, sb, out, n);
-    return (int)hipGetLastError();
-}
-extern "C" int iaf_affine_transform(const float* z, const float* m, const float* s, float scale, float* out, size_t n, void* stream) {
-    if (!z || !m || !s || !out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_affine_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, z, m, s, scale, out, n);
-    return (int)hipGetLastError();
-}
-extern "C" int iaf_clip(const float* x, float lo, float hi, float* out, size_t n, void* stream) {
-    if (!x || !out) return IAF_ERR_NULL;
-    if (n == 0) return IAF_ERR_SHAPE;
-    hipLaunchKernelGGL(iaf_clip_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, x, lo, hi, out, n);
-    return (int)hipGetLastError();
 }

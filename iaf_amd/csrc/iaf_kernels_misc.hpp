@@ -1,7 +1,6 @@
-// iaf_kernels_misc.hpp -- small forward kernels: KL / free-bits reductions, Gaussian sample/logps, max-diff, streaming lower bound, evaluation tail, data-dependent init, discretized logistic.
-// Part of the single translation unit iaf_engine.hip (included there, in order; not a standalone header).
+// iaf_kernels_misc.hpp -- the small kernels the stack's own entry points launch: KL / free-bits reductions, max-diff, the control kernels of the inverse step.
+// Included by iaf_engine.hip and by no other unit (the objective-side kernels: iaf_kernels_objective.hpp, in iaf_model_ops.hip).
 #pragma once
-#include "iaf_common.hpp"   // iaf_nonfinite, iaf_block_sum_f64 (the evaluation tail)
 
 // ---------------------------------------------------------------------------------------------
 // KL / free-bits reduction, tf_train.py:77-85.  kl_elem [B,Z,H,W] -> kl_cost[B], kl_obj[B].
@@ -120,9 +119,6 @@ __global__ __launch_bounds__(256) void iaf_kl_partsum_kernel(const float* part, 
     S[i] = a;
 }
 
-// ---------------------------------------------------------------------------------------------
-// elementwise distributions (tf_utils/distributions.py)
-// ---------------------------------------------------------------------------------------------
 // max |a - b| over n elements -> *out (float bits; non-negative floats order like unsigned ints).  NaN counts as +inf.
 __global__ __launch_bounds__(256) void iaf_maxdiff_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n,
                                                          unsigned* out) {
@@ -183,272 +179,3 @@ __global__ __launch_bounds__(256) void iaf_inverse_finish_kernel(const float* __
     if (!(skipping && done && ((max_sweeps - (int)sw) & 1))) return;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) z0[i] = other[i];
 }
-
-// lvs: 1 when the second tensor holds log-variances (distributions.py), 2 when it holds log standard deviations (the callers'
-// `2 * logsd`: tf_train.py:56-57, rand.py:81-86 -- exact in fp32, so the bits are those of a separate doubling)
-__global__ void iaf_gauss_sample_kernel(const float* mean, const float* logvar, const float* noise, float* out, size_t n, float lvs) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        out[i] = mean[i] + expf(0.5f * (lvs * logvar[i])) * noise[i];
-}
-__global__ void iaf_gauss_logps_kernel(const float* mean, const float* logvar, const float* sample, float* out, size_t n, float lvs) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float d = sample[i] - mean[i], lv = lvs * logvar[i];
-        out[i] = -0.5f * (1.8378770664093453f + lv + d * d / expf(lv));
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Backward of models.cvae_layer with posterior 'up_iaf2_nl' (models.py:168-176, 201-210, 295-298, 454-466), the elementwise
-// parts on either side of iaf_step_backward.  kl = logq0 + logdet - logp(z);  G = d obj / d kl (free bits: gate[c] * gscale,
-// else dko[b]).
-//   pre:  dz_tot = dz + G (z - pz_mean) exp(-2 pz_logsd) [+ d_up_z]      (the gradient that enters the IAF step: -G dlogp/dz)
-//         Gf = G                                                           (contiguous, the step's d logdet)
-//         d_down_conv1 = [d_hdet | -G dlt e2 | G (1 - dlt^2 e2)]            (models.py:296-297 channel order)
-//   post: d_up_conv1 = [d_up_hdet | dz0 | dz0 (z0 - qz_mean) - G | dctx]    (models.py:141-143; logq0 = -(log 2pi + 2 qz_logsd + eps^2)/2)
-// d_h / d_up are [B, n_h + n_z, HW] (concat([h_det, z]) order, models.py:176,318), d_up may be NULL (zeros).
-// ---------------------------------------------------------------------------------------------
-struct UpIafBwdP {
-    const float *z, *pz_mean, *pz_logsd, *d_h, *d_up, *gate, *dko;
-    float *dz_tot, *Gf, *d_dc1;
-    const float *dz0, *z0, *qz_mean, *dctx;
-    float* d_uc1;
-    float gscale;
-    int B, n_h, n_z, HW;
-};
-__global__ __launch_bounds__(256) void iaf_up_iaf2_bwd_pre_kernel(UpIafBwdP p) {
-    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per_in = nh + nz, per_out = nh + 2 * nz;
-    const size_t total = (size_t)p.B * per_out;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = i / per_out, r = i - b * per_out;
-        if (r < nh) { p.d_dc1[i] = p.d_h[b * per_in + r]; continue; }                    // d h_det passes through
-        const bool second = r >= nh + nz;
-        const size_t e = r - nh - (second ? nz : 0), zi = b * nz + e;                     // element of a [B, n_z, HW] tensor
-        const int c = (int)(e / p.HW);
-        const float G = p.gate ? p.gate[c] * p.gscale : p.dko[b];
-        const float e2 = expf(-2.0f * p.pz_logsd[zi]), dlt = p.z[zi] - p.pz_mean[zi];
-        if (!second) {
-            float t = p.d_h[b * per_in + nh + e] + G * dlt * e2;
-            if (p.d_up) t += p.d_up[b * per_in + nh + e];
-            p.dz_tot[zi] = t;
-            p.Gf[zi] = G;
-            p.d_dc1[i] = -G * dlt * e2;
-        } else {
-            p.d_dc1[i] = G * (1.0f - dlt * dlt * e2);
-        }
-    }
-}
-__global__ __launch_bounds__(256) void iaf_up_iaf2_bwd_post_kernel(UpIafBwdP p) {
-    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per_in = nh + nz, per_out = 2 * nh + 2 * nz;
-    const size_t total = (size_t)p.B * per_out;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = i / per_out, r = i - b * per_out;
-        if (r < nh) p.d_uc1[i] = p.d_up ? p.d_up[b * per_in + r] : 0.f;
-        else if (r < nh + nz) p.d_uc1[i] = p.dz0[b * nz + (r - nh)];
-        else if (r < nh + 2 * nz) {
-            const size_t zi = b * nz + (r - nh - nz);
-            p.d_uc1[i] = p.dz0[zi] * (p.z0[zi] - p.qz_mean[zi]) - p.Gf[zi];
-        } else p.d_uc1[i] = p.dctx[b * nh + (r - nh - 2 * nz)];
-    }
-}
-
-// the pieces of the streaming log-sum-exp that iaf_eval_tail_kernel (below) shares with the three kernels here: the running sum
-// rescaled to the new maximum plus a chunk's sum, and the bound the state stands for after k weights (distributions.py:62)
-__device__ __forceinline__ float iaf_lb_rescaled_sum(float old_m, float old_s, float new_m, float s) {
-    return (old_m == -INFINITY ? 0.f : old_s * expf(old_m - new_m)) + s;
-}
-__device__ __forceinline__ float iaf_lb_bound(float run_max, float run_sum, int k) {
-    return -(-logf((float)k) + run_max + logf(run_sum));
-}
-
-// streaming logsumexp over k importance weights per image: one wave per image
-__global__ __launch_bounds__(256) void iaf_lb_update_kernel(float* run_max, float* run_sum, const float* log_pxz,
-                                                           const float* sum_kl, int n, int kc) {
-    const int img = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (img >= n) return;
-    const float* a = log_pxz + (size_t)img * kc;
-    const float* b = sum_kl + (size_t)img * kc;
-    float m = -INFINITY;
-    for (int i = lane; i < kc; i += 64) m = fmaxf(m, a[i] - b[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    const float old_m = run_max[img];
-    const float new_m = fmaxf(old_m, m);
-    float s = 0.f;
-    for (int i = lane; i < kc; i += 64) s += expf((a[i] - b[i]) - new_m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) {
-        const float old_s = run_sum[img];
-        run_sum[img] = iaf_lb_rescaled_sum(old_m, old_s, new_m, s);
-        run_max[img] = new_m;
-    }
-}
-__global__ void iaf_lb_init_kernel(float* run_max, float* run_sum, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { run_max[i] = -INFINITY; run_sum[i] = 0.f; }
-}
-__global__ void iaf_lb_finalize_kernel(const float* run_max, const float* run_sum, float* out, int n, int k) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = iaf_lb_bound(run_max[i], run_sum[i], k);   // distributions.py:62
-}
-__global__ void iaf_lb_k1_kernel(const float* log_pxz, const float* sum_kl, float* out, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = sum_kl[i] - log_pxz[i];                                 // distributions.py:57
-}
-
-// ---------------------------------------------------------------------------------------------
-// data-dependent init, tf_utils/layers.py:45-51: per-channel moments of x_init = conv(x, l2norm(mask*V)) over (N,H,W),
-//   scale = init_scale / sqrt(var + 1e-10);  g = log(scale)/3;  b = -mean*scale;  y = scale*(x_init - mean)
-// One workgroup per channel; two passes (mean, then centred variance) in a fixed tree order.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__global__ __launch_bounds__(256) void iaf_datainit_kernel(const float* x, const float* __restrict__ add, float* y,
-                                                          float* __restrict__ g, float* __restrict__ b, int B, int C, int HW,
-                                                          float init_scale) {
-    __shared__ float red[4];
-    const int c = blockIdx.x;
-    const int n = B * HW;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) { const int bb = i / HW; s += x[((size_t)bb * C + c) * HW + (i - bb * HW)]; }
-    const float mean = block_sum_256(s, red) / (float)n;
-    float q = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int bb = i / HW;
-        const float d = x[((size_t)bb * C + c) * HW + (i - bb * HW)] - mean;
-        q += d * d;
-    }
-    const float var = block_sum_256(q, red) / (float)n;          // tf.nn.moments: biased
-    const float scale = init_scale / sqrtf(var + 1e-10f);
-    if (threadIdx.x == 0) { g[c] = logf(scale) / 3.0f; b[c] = -mean * scale; }
-    if (y)
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const int bb = i / HW;
-            const size_t o = ((size_t)bb * C + c) * HW + (i - bb * HW);
-            y[o] = scale * (x[o] - mean) + (add ? add[o] : 0.f);
-        }
-}
-
-// discretized logistic log-likelihood, tf_utils/distributions.py:28-32 (call site tf_train.py:210): one workgroup per
-// batch row, out[b] = sum log(sigmoid(s + binsize/scale) - sigmoid(s) + 1e-7), s = (floor(x/binsize)*binsize - mean)/scale
-// (the row sum is a helper of its own: iaf_eval_tail_kernel below takes log_pxz from it too, bit for bit)
-__device__ __forceinline__ float iaf_disc_logistic_row(const float* __restrict__ mean, const float* __restrict__ logscale,
-                                                       int scalar_scale, const float* __restrict__ sample, size_t base, size_t n,
-                                                       float binsize, float* red) {
-    float acc = 0.f;
-    for (size_t i = threadIdx.x; i < n; i += 256) {
-        const float scale = expf(scalar_scale ? logscale[0] : logscale[base + i]);
-        const float s = (floorf(sample[base + i] / binsize) * binsize - mean[base + i]) / scale;
-        // sigmoid(s+d) - sigmoid(s), evaluated on the side where both terms are small (sigmoid(t) = 1 - sigmoid(-t)):
-        // the literal fp32 form cancels to ~1e-7 absolute in the upper tail, the size of the +1e-7 floor itself
-        const float d = binsize / scale;
-        float diff;
-        if (s > 0.f) {
-            const float e0 = expf(-s), e1 = expf(-(s + d));
-            diff = e0 / (1.0f + e0) - e1 / (1.0f + e1);
-        } else {
-            diff = 1.0f / (1.0f + expf(-(s + d))) - 1.0f / (1.0f + expf(-s));
-        }
-        acc += logf(diff + 1e-7f);
-    }
-    return block_sum_256(acc, red);
-}
-__global__ __launch_bounds__(256) void iaf_disc_logistic_kernel(const float* __restrict__ mean, const float* __restrict__ logscale,
-                                                               int scalar_scale, const float* __restrict__ sample,
-                                                               float* __restrict__ out, size_t n, float binsize) {
-    __shared__ float red[4];
-    const float tot = iaf_disc_logistic_row(mean, logscale, scalar_scale, sample, (size_t)blockIdx.x * n, n, binsize, red);
-    if (threadIdx.x == 0) out[blockIdx.x] = tot;
-}
-
-// out[j] of iaf_colsum_kernel (csrc/iaf_conv3x3_host.hpp): ((0 + mat[0][j]) + mat[1][j]) + ..., row order
-__device__ __forceinline__ float iaf_col_sum(const float* __restrict__ mat, int m, int n, int j) {
-    float s = 0.f;
-    for (int i = 0; i < m; ++i) s += mat[(size_t)i * n + j];
-    return s;
-}
-
-// ---------------------------------------------------------------------------------------------
-// The tail of one evaluation pass (tf_train.py:210, 198-200, 218 and run_eval's accumulation, :313-325) as ONE launch: what
-// iaf_disc_logistic_kernel, iaf_colsum_kernel, iaf_lb_update_kernel (kc = 1), iaf_lb_finalize_kernel and a sum over the batch do,
-// with the same helpers in the same order -- one workgroup per batch row.  The record counts the passes of the current batch, so a
-// replayed graph needs no host to say which pass closes the batch; the last workgroup to arrive (an agent-scope counter, as in
-// iaf_guard_sumsq_scan_kernel above) adds the closed batch to the epoch's sums and moves the pass counter.  Only thread 0 of a
-// workgroup reads the counter, before it arrives: the last workgroup's write cannot race a read of the same launch.
-// ---------------------------------------------------------------------------------------------
-struct EvalRec { double loss_sum; unsigned long long images, nonfinite; unsigned pass, arrivals; };
-__global__ __launch_bounds__(256) void iaf_eval_tail_kernel(const float* __restrict__ x_out, const float* __restrict__ dec_log_stdv,
-                                                           const float* __restrict__ x, size_t n_per_row, float binsize,
-                                                           const float* __restrict__ layer_cost, int n_layers, int n, float* run_max,
-                                                           float* run_sum, int k, const long long* __restrict__ indices,
-                                                           float* per_image, float* bound, EvalRec* rec) {
-    __shared__ float red[4];
-    __shared__ double red64[4];
-    __shared__ unsigned s_pass, s_last;
-    const int b = blockIdx.x;
-    unsigned p = 0u;
-    float kl = 0.f;
-    if (threadIdx.x == 0) {
-        p = __hip_atomic_load(&rec->pass, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_pass = p;
-        kl = iaf_col_sum(layer_cost, n_layers, n, b);
-    }
-    const float log_pxz = iaf_disc_logistic_row(x_out, dec_log_stdv, 1, x, (size_t)b * n_per_row, n_per_row, binsize, red);
-    if (threadIdx.x == 0) {
-        const bool closing = p + 1u >= (unsigned)k;
-        const float w = log_pxz - kl;
-        const float old_m = run_max[b], old_s = run_sum[b];
-        const float new_m = fmaxf(old_m, fmaxf(-INFINITY, w));                        // iaf_lb_update_kernel, one weight
-        float s = 0.f;
-        s += expf(w - new_m);
-        float rs = iaf_lb_rescaled_sum(old_m, old_s, new_m, s), rm = new_m;
-        if (closing) {
-            const float bd = iaf_lb_bound(rm, rs, k);
-            // (agent scope: the workgroup that sums the bounds may sit on another XCD)
-            __hip_atomic_store((unsigned*)bound + b, __float_as_uint(bd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (per_image) per_image[indices[b]] = bd;
-            rm = -INFINITY; rs = 0.f;                                                  // armed for the next batch
-        }
-        run_max[b] = rm;
-        run_sum[b] = rs;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                               // the bound is in memory before this workgroup arrives
-        s_last = __hip_atomic_fetch_add(&rec->arrivals, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    const unsigned pass = s_pass;
-    const bool closing = pass + 1u >= (unsigned)k;
-    if (closing) {
-        // fixed order: thread t adds rows t, t + 256, ... in index order, then the shuffle / LDS tree; no float atomics
-        double sum = 0.0, bad = 0.0;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const float v = __uint_as_float(__hip_atomic_load((unsigned*)bound + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            sum += (double)v;
-            bad += iaf_nonfinite(v) ? 1.0 : 0.0;                                       // (a count below 2^53: exact)
-        }
-        sum = iaf_block_sum_f64(sum, red64);
-        bad = iaf_block_sum_f64(bad, red64);
-        if (threadIdx.x == 0) {
-            rec->loss_sum += sum;
-            rec->images += (unsigned long long)n;
-            rec->nonfinite += (unsigned long long)bad;
-        }
-    }
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(&rec->pass, closing ? 0u : pass + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&rec->arrivals, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-// zeroes the record and arms the streaming state of n rows
-__global__ __launch_bounds__(256) void iaf_eval_reset_kernel(EvalRec* rec, float* run_max, float* run_sum, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { run_max[i] = -INFINITY; run_sum[i] = 0.f; }
-    if (i == 0) { rec->loss_sum = 0.0; rec->images = 0ull; rec->nonfinite = 0ull; rec->pass = 0u; rec->arrivals = 0u; }
-}
-

@@ -1,6 +1,7 @@
 // iaf_kernels_resample.hpp -- what the DOWNSAMPLING IAFLayer needs on top of the stride-1 convs (tf_train.py:33,42-43,
-// 89-91): 2x resampling in both directions and the weight prep of deconv2d (tf_utils/layers.py:67-112, 169-175).
-// Part of the single translation unit iaf_engine.hip (included there, in order; not a standalone header).
+// 89-91): the weight prep of deconv2d and its backward (tf_utils/layers.py:67-112), which the conv host code launches.
+// Included by iaf_engine.hip and by no other unit.  (The 2x resampling itself, iaf_resample2_kernel, takes no conv:
+// iaf_kernels_objective.hpp.)
 //
 // The two strided ops are expressed through the stride-1 3x3 conv kernel:
 //   conv2d(stride 2, SAME)      out[i,j] = c[2i+1, 2j+1] of the stride-1 SAME conv c (TF pads bottom/right only when
@@ -9,37 +10,6 @@
 //                               the 180-degree-rotated filter:  out[y,x,o] = sum x[(y-a)/2,(x-b)/2,c] f[a,b,o,c]
 // Both cost 4x the minimal MFMA work, for ONE layer per resolution change (1 of 20 at the BASELINE config).
 #pragma once
-
-#define IAF_RESAMPLE_DOWN_EVEN 0   // dst[i,j] = src[2i, 2j]       == resize_nearest_neighbor(x, 0.5) (layers.py:169-175)
-#define IAF_RESAMPLE_DOWN_ODD 1    // dst[i,j] = src[2i+1, 2j+1]   the outputs a stride-2 SAME 3x3 conv keeps
-#define IAF_RESAMPLE_UP_NEAREST 2  // dst[y,x] = src[y/2, x/2]     == resize_nearest_neighbor(x, 2)
-#define IAF_RESAMPLE_UP_ZERO_ODD 3 // dst[2i+1,2j+1] = src[i,j], 0 elsewhere: the zero-inserted input of conv2d_transpose
-// ... and the adjoints the backward pass needs (UP_ZERO_ODD is DOWN_ODD's, and the other way round):
-#define IAF_RESAMPLE_UP_ZERO_EVEN 4 // dst[2i,2j] = src[i,j], 0 elsewhere: adjoint of DOWN_EVEN
-#define IAF_RESAMPLE_DOWN_SUM4 5    // dst[i,j] = sum of src[2i..2i+1, 2j..2j+1]: adjoint of UP_NEAREST
-
-// H, W: size of the SMALLER of the two tensors
-__global__ __launch_bounds__(256) void iaf_resample2_kernel(const float* __restrict__ src, float* __restrict__ dst, size_t n_dst,
-                                                           int H, int W, int mode) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_dst; i += stride) {
-        if (mode == IAF_RESAMPLE_DOWN_EVEN || mode == IAF_RESAMPLE_DOWN_ODD || mode == IAF_RESAMPLE_DOWN_SUM4) {
-            const int x = (int)(i % W), y = (int)((i / W) % H);
-            const size_t plane = i / ((size_t)W * H);
-            const int o = (mode == IAF_RESAMPLE_DOWN_ODD) ? 1 : 0;
-            const float* q = src + (plane * 2 * H + 2 * y + o) * 2 * W + 2 * x + o;
-            dst[i] = (mode == IAF_RESAMPLE_DOWN_SUM4) ? (q[0] + q[1]) + (q[2 * W] + q[2 * W + 1]) : q[0];
-        } else {
-            const int W2 = 2 * W, H2 = 2 * H;
-            const int x = (int)(i % W2), y = (int)((i / W2) % H2);
-            const size_t plane = i / ((size_t)W2 * H2);
-            const float v = src[(plane * H + (y >> 1)) * W + (x >> 1)];
-            const bool keep = mode == IAF_RESAMPLE_UP_NEAREST || (mode == IAF_RESAMPLE_UP_ZERO_ODD && (y & 1) && (x & 1)) ||
-                              (mode == IAF_RESAMPLE_UP_ZERO_EVEN && !(y & 1) && !(x & 1));
-            dst[i] = keep ? v : 0.f;
-        }
-    }
-}
 
 // deconv2d weight norm (layers.py:104): l2_normalize(V, [0,1,2]) with V [3,3,n_out,n_in] -> one norm per INPUT channel
 __global__ __launch_bounds__(256) void iaf_deconv_norm_kernel(const float* __restrict__ V, float* __restrict__ inv_norm,

@@ -2,7 +2,7 @@
 image scaling, conv2d("x_enc", 5x5, stride 2), the bottom-up pass through depth x num_blocks IAFLayers, the tiled h_top, the
 top-down pass accumulating kl_obj / kl_cost, deconv2d("x_dec", 5x5) + clip, discretized_logistic, obj and the (k-sample) loss.
 Every number is computed by HIP launches behind the C ABI (include/iaf_hip.h); torch tensors are storage.  The two edge convs
-have 3 channels on one side and run as direct convolutions (csrc/iaf_model_edge.hpp); the layers are iaf_amd.IAFLayer.
+have 3 channels on one side and run as direct convolutions (csrc/iaf_kernels_edge.hpp); the layers are iaf_amd.IAFLayer.
 forward() for every mode; forward_backward() = one tower's training objective and its gradient w.r.t. every variable (mode "train",
 k = 1): the layers' backward (IAFLayer.down_backward / .up_backward) chained through the model + the backward of the two ends."""
 import math
@@ -687,7 +687,7 @@ class CVAE1(object):
         autotune=True: the first call at a new batch size searches the launch shapes of the plain convs and their data gradients (what
         cuDNN's algorithm search does for the reference).  The layer stack's backward is IAFLayer.down_backward / .up_backward chained through the model (the down pass
         in up-pass order, then the up pass in reverse); the two ends -- likelihood, clip, x_dec, h_top, x_enc -- are the launches of
-        csrc/iaf_model_edge.hpp.  noise as in forward().  on_bucket(i): called as soon as the gradients of bucket i (set_grad_buckets) are
+        csrc/iaf_model_ops.hip.  noise as in forward().  on_bucket(i): called as soon as the gradients of bucket i (set_grad_buckets) are
         complete on the current stream -- where a data-parallel step issues that bucket's all-reduce (OverlappedGradReduce.reduce)."""
         F = self.fb_begin(x, noise, grads, autotune)
         for si in range(len(self._segs)):

@@ -1,4 +1,4 @@
-"""torch-fp64 statements of the backward operations of the model's two ends (iaf_amd/csrc/iaf_model_edge.hpp), written from the
+"""torch-fp64 statements of the backward operations of the model's two ends (iaf_amd/csrc/iaf_kernels_edge.hpp), written from the
 reference's lines as oracle/iaf_grad_oracle.py:cvae1_obj restates them (tf_train.py:183, 206-211; tf_utils/layers.py:56-60, 67-80,
 104-111; tf_utils/distributions.py:28-32) and differentiated by autograd; a plain fp32 restatement of the likelihood's gradient that
 the device kernel's error is measured against; and the seed-fixed inputs of the likelihood cases, so that the CPU test of the

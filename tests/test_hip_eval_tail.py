@@ -1,4 +1,4 @@
-"""GPU leaf test of iaf_eval_tail / iaf_eval_reset (include/iaf_hip.h; iaf_amd/csrc/iaf_kernels_misc.hpp: iaf_eval_tail_kernel) through
+"""GPU leaf test of iaf_eval_tail / iaf_eval_reset (include/iaf_hip.h; iaf_amd/csrc/iaf_kernels_objective.hpp: iaf_eval_tail_kernel) through
 the raw C ABI: the one launch that closes an evaluation pass against the entry points it replaces, called on the same device
 buffers -- iaf_discretized_logistic -> iaf_colsum -> iaf_lowerbound_stream_update(k_chunk = 1) per pass, iaf_lowerbound_stream_finalize
 (and, for k = 1, iaf_compute_lowerbound) behind the k-th.  The criterion is BIT IDENTITY: the kernel's summation orders are those

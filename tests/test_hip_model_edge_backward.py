@@ -1,4 +1,4 @@
-"""GPU leaf tests of the backward kernels of the model's two ends (iaf_amd/csrc/iaf_model_edge.hpp) and of the adjoint modes of
+"""GPU leaf tests of the backward kernels of the model's two ends (iaf_amd/csrc/iaf_kernels_edge.hpp) and of the adjoint modes of
 iaf_resample2, one by one through the raw C ABI against the torch-fp64 references of tests/model_edge_reference.py (pinned on the
 CPU by tests/test_model_edge_reference.py): iaf_discretized_logistic_backward (centre, both tails, mirror identity, clip gate),
 iaf_convk_wgrad (every tap on its own), iaf_convk_weightnorm_backward (conv and deconv form, clamped channel), iaf_channel_sum,

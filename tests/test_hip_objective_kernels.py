@@ -1,5 +1,5 @@
-"""GPU leaf tests of the objective-side kernels (iaf_amd/csrc/iaf_kernels_misc.hpp and the elementwise entry points of the init
-pass), one by one through the raw C ABI against the fp64 references of tests/objective_reference.py (pinned on the CPU by
+"""GPU leaf tests of the objective-side kernels (iaf_amd/csrc/iaf_kernels_objective.hpp, the free-bits kernels of iaf_kernels_misc.hpp and the
+elementwise entry points of the init pass, iaf_kernels_edge.hpp), one by one through the raw C ABI against the fp64 references of tests/objective_reference.py (pinned on the CPU by
 tests/test_objective_reference.py): iaf_kl_free_bits / iaf_kl_free_bits_gate on every route of the finish kernel that takes plain row sums, the same
 reductions behind iaf_posterior_block_forward, iaf_compute_lowerbound and the streaming trio, iaf_discretized_logistic per element
 and per row, the four iaf_gaussian_* entry points, iaf_datainit_normalize, iaf_colsum, iaf_kl_combine, iaf_axpby,
