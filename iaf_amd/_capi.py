@@ -191,6 +191,8 @@ SIGNATURES = {
                                                   ctypes.c_int, _vp]),
     "iaf_conv3x3_forward_prior_sample": (ctypes.c_int, [_vp, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p,
                                                         _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "iaf_conv3x3_forward_hdet": (ctypes.c_int, [_vp, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, _vp]),
     "iaf_conv3x3_prep_batch_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int]),
     "iaf_conv3x3_prep_batch_run": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "iaf_conv3x3_prep_batch_destroy": (ctypes.c_int, [_vp]),

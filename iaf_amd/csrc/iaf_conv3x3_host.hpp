@@ -453,15 +453,32 @@ extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float
 // conv's size rule (fewest workgroups per 32-pixel block that still fill the chip, at most an eighth of the tiles ragged) on the LAUNCHED
 // tiles, with NT in {2, 4} (two-tile units).  Arithmetic: two fp16 planes where the forward at this size runs them
 // (iaf_conv3x3_runs_f16x2, same range word and protocol), else the bf16x3 planes at any size (fp32-grade; there is no fp32-kernel form).
-static conv_fn_t conv3x3_prior_shape(const GemmLayer& L, int nlt, long long P, int W, bool f16, int* nt_out, int* wco_out, size_t* lds_out) {
+// ragged_den: at most 1 / ragged_den of the tiles may be ragged (8: the plain conv's bound, and the prior form's).  The h_det-only form's is
+// a fifth -- 12 launched tiles for the 10 of h 160, NT 4 x WCO 3: ONE workgroup per 32-pixel block where it fills the chip (the tile is
+// staged once instead of five times; measured, DESIGN.md 4.3: 20.2 against 28.4 us at 32 x 16 x 16)
+#ifndef IAF_HDET_RAGGED_DEN
+#define IAF_HDET_RAGGED_DEN 5
+#endif
+static conv_fn_t conv3x3_prior_shape(const GemmLayer& L, int nlt, long long P, int W, bool f16, int* nt_out, int* wco_out, size_t* lds_out,
+                                     int ragged_den = 8, const char* env_name = nullptr) {
     static const int cand[6][2] = {{4, 3}, {4, 2}, {2, 3}, {4, 1}, {2, 2}, {2, 1}};
     const long long nblk = (P + 31) / 32;
     int best = -1;
     long long best_wgs = 0;
+    // env_name (dev override, as IAF_S2_SHAPE): "nt,wco" of a compiled shape, taken if it fits the LDS
+    int env[2] = {0, 0};
+    const char* e = env_name ? getenv(env_name) : nullptr;
+    if (e && sscanf(e, "%d,%d", &env[0], &env[1]) == 2 && env[0] > 0 && env[1] > 0 &&
+        pick_bf3p(env[0], 2, 1, 4, env[1], f16 ? BF3P_PRIOR_F16 : BF3P_PRIOR) &&
+        bf3_plain_lds_bytes(L.cin, W, env[0], 2, 1, 4, env[1], f16 ? 2 : 3) <= 160 * 1024) {
+        *nt_out = env[0]; *wco_out = env[1];
+        *lds_out = bf3_plain_lds_bytes(L.cin, W, env[0], 2, 1, 4, env[1], f16 ? 2 : 3);
+        return pick_bf3p(env[0], 2, 1, 4, env[1], f16 ? BF3P_PRIOR_F16 : BF3P_PRIOR);
+    }
     for (int i = 0; i < 6; ++i) {
         const int nt = cand[i][0], wco = cand[i][1], per = nt * wco;
         const int covered = (nlt + per - 1) / per * per;
-        if ((covered - nlt) * 8 > nlt || !pick_bf3p(nt, 2, 1, 4, wco, f16 ? BF3P_PRIOR_F16 : BF3P_PRIOR)) continue;
+        if ((covered - nlt) * ragged_den > nlt || !pick_bf3p(nt, 2, 1, 4, wco, f16 ? BF3P_PRIOR_F16 : BF3P_PRIOR)) continue;
         if (bf3_plain_lds_bytes(L.cin, W, nt, 2, 1, 4, wco, f16 ? 2 : 3) > 160 * 1024) continue;
         const long long wgs = nblk * (covered / per);
         if (wgs >= 256) { best = i; break; }
@@ -473,12 +490,9 @@ static conv_fn_t conv3x3_prior_shape(const GemmLayer& L, int nlt, long long P, i
     return pick_bf3p(*nt_out, 2, 1, 4, *wco_out, f16 ? BF3P_PRIOR_F16 : BF3P_PRIOR);
 }
 
-extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, const float* eps, float* z,
-                                                float* h_det, int B, int H, int W, void* stream) {
-    if (!c || !x || !eps || !z || !h_det) return IAF_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || n_z <= 0 || n_h <= 0) return IAF_ERR_SHAPE;
-    if ((long long)B * H * W > (1LL << 30) / 64) return IAF_ERR_SHAPE;
-    if (c->n_out != 4 * n_z + 2 * n_h) return IAF_ERR_SHAPE;
+// the launch behind both entry points.  n_zu: the (pz_mean, pz_logsd) units launched -- n_z / 16 (prior form), or 0 (h_det only: eps, z NULL)
+static int conv3x3_prior_launch(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, int n_zu, const float* eps, float* z,
+                                float* h_det, int B, int H, int W, void* stream) {
     GemmLayer& L = c->L;
     if (c->generic || c->mask_mode || c->deconv || !L.wp3 || !conv_split(c) || (n_z & 15) || (n_h & 15)) return IAF_ERR_UNSUPPORTED;
     if (!c->prepared) return IAF_ERR_NOT_PREPARED;
@@ -488,15 +502,21 @@ extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x
     if (!(c->packs & (f16 ? IAF_PACK_F16X2 : IAF_PACK_BF16X3))) return IAF_ERR_NOT_PREPARED;    // (iaf_conv3x3_set_packs)
     ConvP p;
     memset(&p, 0, sizeof(p));
-    p.pr_nzt = n_z / 16; p.pr_nht = n_h / 16; p.pr_nlt = 2 * p.pr_nzt + 2 * ((p.pr_nht + 1) / 2);
+    p.pr_nzt = n_zu; p.pr_nht = n_h / 16; p.pr_nlt = 2 * p.pr_nzt + 2 * ((p.pr_nht + 1) / 2);
     int nt = 0, wco = 0;
     size_t lds = 0;
-    conv_fn_t fn = conv3x3_prior_shape(L, p.pr_nlt, (long long)B * H * W, W, f16, &nt, &wco, &lds);
+    conv_fn_t fn = n_zu ? conv3x3_prior_shape(L, p.pr_nlt, (long long)B * H * W, W, f16, &nt, &wco, &lds)
+                        : conv3x3_prior_shape(L, p.pr_nlt, (long long)B * H * W, W, f16, &nt, &wco, &lds, IAF_HDET_RAGGED_DEN, "IAF_HDET_SHAPE");
     if (!fn) return IAF_ERR_UNSUPPORTED;
     p.B = B; p.H = H; p.W = W; p.HW = H * W; p.P = B * H * W;
     p.x = x; p.in_elu = elu_input ? 1 : 0;
     p.eps = eps; p.out0 = z; p.out1 = h_det;
-    p.wp = f16 ? (const float*)L.wp2 : (const float*)L.wp3; p.bias = L.bias;
+    // the tiles the z units skip, when none is launched: prior_pack_tile counts pack tiles from (4 pr_nzt) on, so with pr_nzt = 0 the pack and
+    // the bias are handed over from down_conv1's tile 4 n_z / 16 on (a tile = npl KiB of every step; the step stride stays the whole pack's,
+    // p.ncot).  The last tile read is pr_nht + pr_nht - 1 behind that = the pack's last.
+    const int skip = 4 * (n_z / 16 - n_zu);
+    const char* pack = f16 ? (const char*)L.wp2 : (const char*)L.wp3;
+    p.wp = (const float*)(pack + (size_t)skip * (f16 ? 2 : 3) * 1024); p.bias = L.bias + (size_t)skip * 16;
     p.rng_err = f16 ? c->rng.dev : nullptr;
     for (int t = 0; t < MAXTAPS; ++t) { p.tap_dh[t] = t / 3 - 1; p.tap_dw[t] = t % 3 - 1; }     // cross-correlation, SAME
     const int tm = 32;                                                                             // ppw 2, pxt 1
@@ -510,6 +530,29 @@ extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x
     p.lds_bytes = (int)lds;
     hipLaunchKernelGGL(fn, grid, dim3(64 * 4 * wco), lds, (hipStream_t)stream, p);
     return (int)hipGetLastError();
+}
+
+extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, const float* eps, float* z,
+                                                float* h_det, int B, int H, int W, void* stream) {
+    if (!c || !x || !eps || !z || !h_det) return IAF_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || n_z <= 0 || n_h <= 0) return IAF_ERR_SHAPE;
+    if ((long long)B * H * W > (1LL << 30) / 64) return IAF_ERR_SHAPE;
+    if (c->n_out != 4 * n_z + 2 * n_h) return IAF_ERR_SHAPE;
+    return conv3x3_prior_launch(c, x, elu_input, n_z, n_h, n_z / 16, eps, z, h_det, B, H, W, stream);
+}
+
+// ---- down_conv1 in h_det-only form: a layer whose z is GIVEN (CVAE1.decode; tf_train.py:52-54, 87-88) ------------------------------------
+// Of down_conv1's six outputs a given z leaves only h_det to compute: n_h / 16 of the (4 n_z + 2 n_h) / 16 co tiles (10 of 28 at z 32 /
+// h 160).  It is the prior form with no z unit (EPI_PRIOR, pr_nzt = 0: every launched unit is a pair of h_det tiles; eps / out0 are never
+// dereferenced -- epi_load / epi_apply touch them for u < pr_nzt only), on the pack handed over from its first skipped tile (above): no
+// kernel of its own.  Arithmetic, range word, fallbacks: the prior form's.
+extern "C" int iaf_conv3x3_forward_hdet(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, float* h_det, int B, int H, int W,
+                                        void* stream) {
+    if (!c || !x || !h_det) return IAF_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || n_z <= 0 || n_h <= 0) return IAF_ERR_SHAPE;
+    if ((long long)B * H * W > (1LL << 30) / 64) return IAF_ERR_SHAPE;
+    if (c->n_out != 4 * n_z + 2 * n_h) return IAF_ERR_SHAPE;
+    return conv3x3_prior_launch(c, x, elu_input, n_z, n_h, 0, nullptr, nullptr, h_det, B, H, W, stream);
 }
 
 // ---- the downsampling IAFLayer's two strided convs at their minimal work (iaf_conv_bf3.hpp, template parameter S2) ------------

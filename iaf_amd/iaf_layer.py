@@ -207,6 +207,10 @@ class IAFLayer(object):
         return out, blk["kl_obj"], blk["kl_cost"]
 
     def _generate_down(self, inp, eps_prior):
+        return self._prior_down(inp, eps_prior)[0]
+
+    def _prior_down(self, inp, eps_prior):
+        """(output, z): the launches of generate_down; z = the prior sample"""
         zs, hs = self.z_size, self.h_size
         _check_act(inp, "inp")
         B, _, H, W = (int(v) for v in inp.shape)
@@ -219,9 +223,53 @@ class IAFLayer(object):
             z = gaussian_sample(pz_mean, pz_logsd, eps_prior)
         else:
             _capi.check(rc)
+        return self._last_conv(z, h_det, inp), z
+
+    def _last_conv(self, z, h_det, inp):
         if self.downsample:                                                                               # :87-91, 94
             return self.down_conv2.deconv(z, x2=h_det, elu_input=True, residual=inp)
         return self.down_conv2(z, x2=h_det, elu_input=True, residual=inp)[0]
+
+    # -- the down pass with the latent's source chosen per call (CVAE1.encode / decode / reconstruct) ------------------------------------
+    def down_from(self, inp, source, eps=None, kl_cost_out=None):
+        """down() (tf_train.py:46-95) with z taken from `source`, whatever self.mode:
+          "posterior"  the launches of down() in mode "train": eps = the posterior noise; needs the state up() left (:38)
+          "prior"      the launches of generate_down(): eps = the prior noise
+          a tensor     [B,z_size,H,W], the latent itself: only h_det of down_conv1 is computed (WNConv2d.hdet), then the last conv
+        Returns (output, z, kl_cost): z = the latent the last conv read (post-flow, :71, for "posterior"), kl_cost [B] (:85) for
+        "posterior" -- written into kl_cost_out, a contiguous fp32 [B] tensor, where given -- else None."""
+        if isinstance(source, str):
+            if source not in ("posterior", "prior"):
+                raise ValueError("source: 'posterior', 'prior' or the latent tensor, got %r" % (source,))
+            if eps is None:
+                raise ValueError("source %r draws its latent: pass eps" % (source,))
+            if source == "posterior" and self.posterior.qz_mean is None:
+                raise RuntimeError("source 'posterior' reads what up() leaves in the layer (tf_train.py:38): run the bottom-up pass first")
+        elif not torch.is_tensor(source):
+            raise ValueError("source: 'posterior', 'prior' or the latent tensor, got %r" % (type(source),))
+        return self._range_retry(self._down_from, inp, source, eps, kl_cost_out)
+
+    def _down_from(self, inp, source, eps, kl_cost_out):
+        zs, hs = self.z_size, self.h_size
+        if isinstance(source, str) and source == "prior":
+            out, z = self._prior_down(inp, eps)
+            return out, z, None
+        if isinstance(source, str):                                                                       # "posterior": as _down, mode "train"
+            pz_mean, pz_logsd, rz_mean, rz_logsd, down_context, h_det = self.down_conv1(inp, elu_input=True, split=[zs] * 4 + [hs] * 2)
+            blk = self.posterior.down(pz_mean, pz_logsd, rz_mean, rz_logsd, down_context, eps,
+                                      out=None if kl_cost_out is None else dict(kl_cost=kl_cost_out))
+            self.last_block = blk
+            return self._last_conv(blk["z"], h_det, inp), blk["z"], blk["kl_cost"]
+        _check_act(inp, "inp")
+        B, _, H, W = (int(v) for v in inp.shape)
+        _check_act(source, "z", (B, zs, H, W))
+        rc, h_det = self.down_conv1._hdet(inp, zs, elu_input=True)                                        # :52-54: the sixth piece only
+        if rc in (_capi.IAF_ERR_UNSUPPORTED, _capi.IAF_ERR_NOT_PREPARED):
+            # no such form for this conv, or trim_packs kept only the fp32 pack: the full down_conv1 (as _prior_down)
+            h_det = self.down_conv1(inp, elu_input=True, split=[zs] * 4 + [hs] * 2)[5]
+        else:
+            _capi.check(rc)
+        return self._last_conv(source, h_det, inp), source, None
 
     # -- training: forward that keeps what the backward needs, and the backward (tf_train.py:138 for this layer) -----
     def set_training(self, on=True):

@@ -824,6 +824,27 @@ class WNConv2d(object):
                                                           _ptr(h_det), B, H, W, _stream())
         return rc, z, h_det
 
+    def hdet(self, x, n_z, elu_input=True):
+        """down_conv1 of a layer whose latent is given (tf_train.py:52-54, 87-88; iaf_conv3x3_forward_hdet): of the split [n_z x 4, n_h x 2]
+        only h_det is computed.  x [B,n_in,H,W]; returns h_det [B,n_h,H,W].  UnsupportedError where no such form exists
+        (IAFLayer.down_from then runs __call__ and takes its sixth piece)."""
+        rc, h_det = self._hdet(x, n_z, elu_input)
+        _capi.check(rc)
+        return h_det
+
+    def _hdet(self, x, n_z, elu_input=True):
+        """hdet's launch: (status, h_det) -- argument errors raise here, the engine's status is the caller's to check"""
+        _check_act(x, "x")
+        B, c1, H, W = (int(v) for v in x.shape)
+        if c1 != self.n_in:
+            raise ValueError("x has %d channels, expected %d" % (c1, self.n_in))
+        n_z = int(n_z)
+        n_h2 = self.n_out - 4 * n_z
+        if n_z <= 0 or n_h2 <= 0 or n_h2 % 2:
+            raise ValueError("n_out = %d is not 4*n_z + 2*n_h for n_z = %d" % (self.n_out, n_z))
+        h_det = torch.empty((B, n_h2 // 2, H, W), device=x.device, dtype=torch.float32)
+        rc = _capi.lib().iaf_conv3x3_forward_hdet(self._h, _ptr(x), 1 if elu_input else 0, n_z, n_h2 // 2, _ptr(h_det), B, H, W, _stream())
+        return rc, h_det
 
     def stride2(self, x, elu_input=False, split=None):
         """conv2d(..., stride=[2,2]) (tf_train.py:33,36) at its minimal work: x [B,n_in,2H,2W] -> split tensors [B,.,H,W].

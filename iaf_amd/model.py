@@ -16,6 +16,27 @@ from .layers import (check_groups, ConvPrepBatch, PrepBatch, VariableStore, WnBw
                      _stream)
 
 
+def lerp_latents(za, zb, alpha, out=None):
+    """(1 - alpha) za + alpha zb, layer by layer: interpolation between two sets of codes (CVAE1.encode()'s z lists; the result goes to
+    CVAE1.decode).  One iaf_axpby launch per layer, no torch op; alpha 0 / 1 return the endpoints' values exactly.  out: a list from an
+    earlier call -- its tensors are refilled (a captured graph's static buffers)."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha):
+        raise ValueError("alpha must be a finite number, got %r" % (alpha,))
+    if not isinstance(za, (list, tuple)) or not isinstance(zb, (list, tuple)) or len(za) != len(zb) or len(za) < 1:
+        raise ValueError("za, zb: two lists of latents of the same length")
+    if out is not None and (not isinstance(out, (list, tuple)) or len(out) != len(za)):
+        raise ValueError("out: a list of %d tensors" % len(za))
+    for li, (a, b) in enumerate(zip(za, zb)):
+        _check_act(a, "za[%d]" % li)
+        _check_act(b, "zb[%d]" % li, tuple(a.shape))
+        if out is not None:
+            _check_act(out[li], "out[%d]" % li, tuple(a.shape))
+    res = [torch.empty_like(a) for a in za] if out is None else list(out)
+    for a, b, o in zip(za, zb, res):
+        _capi.check(_capi.lib().iaf_axpby(_ptr(a), 1.0 - float(alpha), _ptr(b), float(alpha), _ptr(o), a.numel(), _stream()))
+    return res
+
+
 class CVAE1(object):
     """Same hyper-parameters as the reference's HParams (tf_train.py:98-112) that _forward reads: z_size, h_size, kl_min, depth
     (number of resolution levels), num_blocks (layers per level), k (importance samples), image_size.  `mode` as in the
@@ -391,6 +412,129 @@ class CVAE1(object):
                     raise ValueError("eps_prior[%d]: a contiguous fp32 device tensor [%d,%d,%d,%d]" % (li, B, self.z_size, Sl, Sl))
                 li += 1
         return B
+
+    # -- the latents: one top-down pass in which every layer takes its z from the posterior, from the prior, or from the caller ------------
+    def _layers_top_down(self):
+        """[(layer, resolution of its latent)] in the order the down pass runs (tf_train.py:195-200)"""
+        return [(layer, self.image_size // 2 ** (i + 1)) for i in reversed(range(self.depth)) for layer in reversed(self.layers[i])]
+
+    def _check_latent_call(self, what):
+        if self.params is None:
+            raise RuntimeError("CVAE1.load(params) first")
+        if self.k != 1:
+            raise ValueError("%s works on one sample per image: build the model with k = 1" % what)
+
+    def _check_sources(self, sources, noise):
+        """what _top_down_mixed requires (host-only checks, before any launch); returns (B, device)"""
+        nl = self.depth * self.num_blocks
+        if not isinstance(sources, (list, tuple)) or len(sources) != nl:
+            raise ValueError("sources: %d entries expected ('posterior', 'prior' or a latent per layer, top-down)" % nl)
+        if not isinstance(noise, (list, tuple)) or len(noise) != 2 * nl:
+            raise ValueError("noise: %d entries expected (prior, posterior per layer, top-down; None where not read)" % (2 * nl))
+        read = [s if torch.is_tensor(s) else noise[2 * li + (1 if s == "posterior" else 0)] if isinstance(s, str) and s in ("posterior", "prior")
+                else None for li, s in enumerate(sources)]
+        t0 = read[0]
+        if not torch.is_tensor(t0) or t0.dim() != 4 or int(t0.shape[0]) < 1:
+            raise ValueError("layer 0: 'posterior' / 'prior' with its noise tensor, or a latent [B,%d,S_l,S_l]" % self.z_size)
+        B, dev = int(t0.shape[0]), t0.device
+        for li, ((layer, Sl), s, t) in enumerate(zip(self._layers_top_down(), sources, read)):
+            if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.device != dev
+                    or tuple(t.shape) != (B, self.z_size, Sl, Sl)):
+                raise ValueError("layer %d (%s): a contiguous fp32 device tensor [%d,%d,%d,%d]"
+                                 % (li, s if isinstance(s, str) else "latent", B, self.z_size, Sl, Sl))
+            if isinstance(s, str) and s == "posterior":
+                q = layer.posterior.qz_mean
+                if q is None or int(q.shape[0]) != B:
+                    raise RuntimeError("layer %d: 'posterior' reads what the bottom-up pass of these %d images leaves in the layer" % (li, B))
+        return B, dev
+
+    def _top_down_mixed(self, sources, noise, out=None, cost_rows=None):
+        """tf_train.py:189-208 with the latent of every layer taken from sources[l] (top-down): "posterior" (IAFLayer.down in mode "train" on
+        the state _bottom_up left, noise[2l+1]), "prior" (generate_down, noise[2l]) or the latent itself (IAFLayer.down_from).  noise:
+        forward()'s list; slots not read may be None.  out: a contiguous [B,3,S,S] tensor (or slice) x_out is written into.  cost_rows: a
+        [nl, B] matrix whose row l a "posterior" layer writes its kl_cost into.  Returns (x_out, [z of every layer]).  No host
+        synchronisation: capturable with torch.cuda.graph."""
+        B, dev = self._check_sources(sources, noise)
+        lib, p, hs, S = _capi.lib(), self.params, self.h_size, self.image_size
+        if out is None:
+            out = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+        else:
+            _check_act(out, "out", (B, 3, S, S))
+        St = S // 2 ** self.depth
+        h = torch.empty((B, hs, St, St), dtype=torch.float32, device=dev)
+        _capi.check(lib.iaf_tile_channels(_ptr(p["h_top"]), _ptr(h), B, hs, St * St, _stream()))          # :189-192
+        zs = []
+        for li, ((layer, _), s) in enumerate(zip(self._layers_top_down(), sources)):                       # :195-200
+            eps = None if torch.is_tensor(s) else noise[2 * li + (1 if s == "posterior" else 0)]
+            h, z, _ = layer.down_from(h, s, eps, kl_cost_out=None if cost_rows is None or torch.is_tensor(s) or s != "posterior" else cost_rows[li])
+            zs.append(z)
+        _capi.check(lib.iaf_deconvk_forward(_ptr(h), _ptr(self._w_dec), _ptr(p["x_dec/b"]), _ptr(out), B, hs, S // 2, S // 2, 3, 5, 5,
+                                            2, 1, -0.5 + 1 / 512., 0.5 - 1 / 512., _stream()))             # :206-208
+        return out, zs
+
+    def _check_read_slots(self, noise, posterior_layers):
+        """reconstruct's noise: the posterior slots of the first posterior_layers layers and the prior slots of the rest must be there"""
+        nl = self.depth * self.num_blocks
+        for li in range(nl):
+            slot = 2 * li + (1 if li < posterior_layers else 0)
+            if noise[slot] is None:
+                raise ValueError("noise[%d] is None: layer %d reads its %s noise" % (slot, li, "posterior" if li < posterior_layers else "prior"))
+
+    def encode(self, x, noise):
+        """The codes of a batch of images: the bottom-up pass, then the top-down pass with every latent drawn from the posterior (what
+        forward() computes in mode "train", whatever mode the model was built with).  x uint8 [B,3,S,S]; noise: forward()'s list (the
+        posterior slots are read, the prior ones may be None).  Returns dict(z = [the post-flow latent of every layer (tf_train.py:71),
+        top-down, B x z_size x S_l x S_l], x_out [B,3,S,S], kl_cost [nl, B] (:85, row l = layer l))."""
+        self._check_latent_call("encode")
+        B, _, _ = self._check_inputs(x, noise, 1)
+        nl = self.depth * self.num_blocks
+        self._check_read_slots(noise, nl)
+        self._bottom_up(x, noise)
+        cost_rows = torch.empty((nl, B), dtype=torch.float32, device=x.device)
+        x_out, zs = self._top_down_mixed(["posterior"] * nl, noise, cost_rows=cost_rows)
+        return dict(z=zs, x_out=x_out, kl_cost=cost_rows)
+
+    def decode(self, z, eps_prior=None):
+        """Images from codes: the top-down pass alone (no image, no bottom-up pass).  z: per layer in top-down order the latent
+        [B,z_size,S_l,S_l] (encode()'s, edited or interpolated: iaf_amd.lerp_latents), or None = sample that layer from the prior with
+        eps_prior[l] (generate()'s list; entries of given layers may be None).  All None is generate(eps_prior).  Returns x_out [B,3,S,S]."""
+        self._check_latent_call("decode")
+        nl = self.depth * self.num_blocks
+        if not isinstance(z, (list, tuple)) or len(z) != nl:
+            raise ValueError("z: %d entries expected (a latent or None per layer, top-down)" % nl)
+        if eps_prior is None:
+            eps_prior = [None] * nl
+        if not isinstance(eps_prior, (list, tuple)) or len(eps_prior) != nl:
+            raise ValueError("eps_prior: %d entries expected (the prior noise of every layer not given, top-down)" % nl)
+        noise = []
+        for li in range(nl):
+            if z[li] is None and eps_prior[li] is None:
+                raise ValueError("layer %d: neither a latent nor prior noise" % li)
+            noise += [eps_prior[li], None]
+        return self._top_down_mixed(["prior" if t is None else t for t in z], noise)[0]
+
+    def reconstruct(self, x, noise, posterior_layers):
+        """x_out with the first `posterior_layers` layers of the top-down pass drawn from the posterior of x and the rest from the prior:
+        what the top levels of the hierarchy carry.  nl (= depth * num_blocks) is forward()'s x_out in mode "train", 0 is
+        generate(noise[0::2]).  noise: forward()'s list (posterior slots of the first layers, prior slots of the rest)."""
+        return self.reconstruct_ladder(x, noise, [posterior_layers])
+
+    def reconstruct_ladder(self, x, noise, steps):
+        """reconstruct() for every entry of `steps` in one contiguous [len(steps) B,3,S,S] tensor, step s in rows s B .. (s+1) B (what
+        image_grid takes): the bottom-up pass runs once for all steps."""
+        self._check_latent_call("reconstruct")
+        B, S, _ = self._check_inputs(x, noise, 1)
+        nl = self.depth * self.num_blocks
+        if not isinstance(steps, (list, tuple)) or len(steps) < 1 or not all(_capi.int_in(n, 0, nl + 1) for n in steps):
+            raise ValueError("posterior_layers: ints in 0 .. %d, got %r" % (nl, steps))
+        for n in steps:
+            self._check_read_slots(noise, n)
+        if max(steps) > 0:
+            self._bottom_up(x, noise)
+        out = torch.empty((len(steps) * B, 3, S, S), dtype=torch.float32, device=x.device)
+        for s, n in enumerate(steps):
+            self._top_down_mixed(["posterior"] * n + ["prior"] * (nl - n), noise, out=out[s * B:(s + 1) * B])
+        return out
 
     def _bottom_up(self, x, noise):
         """tf_train.py:153-187: image scaling (+ repeat k), x_enc, the up pass of every layer (which leaves qz_mean, qz_logsd, up_context in

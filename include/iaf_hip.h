@@ -705,6 +705,17 @@ int iaf_conv3x3_forward_deconv(iaf_conv3x3_t* c, const float* x, const float* x2
  * iaf_conv3x3_forward + iaf_gaussian_sample_logsd; IAF_ERR_NOT_PREPARED as iaf_conv3x3_forward (incl. a pack iaf_conv3x3_set_packs dropped). */
 int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, const float* eps, float* z,
                                      float* h_det, int B, int H, int W, void* stream);
+/* down_conv1 of an IAFLayer whose latent is GIVEN (CVAE1.decode): of [pz_mean, pz_logsd, rz_mean, rz_logsd, down_context, h_det] =
+ * conv2d([elu](x)) split [n_z x 4, n_h x 2] (tf_train.py:52-54) only h_det is read (:87-88), and only its n_h / 16 of the
+ * (4 n_z + 2 n_h) / 16 output tiles are computed, from the conv's own pack.  c: a prepared plain conv with n_out = 4 n_z + 2 n_h.
+ * x [B,n_in,H,W]; h_det [B,n_h,H,W].  Arithmetic as iaf_conv3x3_forward_prior_sample (it is that kernel with no (mean, logsd) unit): two
+ * fp16 planes where iaf_conv3x3_forward at this (B, H, W) runs them (iaf_conv3x3_runs_f16x2; the same range word: IAF_ERR_RANGE once on
+ * the next call, then bf16 planes), else the bf16x3 planes.
+ * Errors: IAF_ERR_NULL / IAF_ERR_SHAPE (n_out != 4 n_z + 2 n_h) before any device work; IAF_ERR_UNSUPPORTED where no such form exists
+ * (n_z or n_h not a multiple of 16, generic channel counts, masked convs, deconvs, IAF_PRECISION_F32): the caller then runs
+ * iaf_conv3x3_forward and takes its sixth piece; IAF_ERR_NOT_PREPARED as iaf_conv3x3_forward (incl. a pack iaf_conv3x3_set_packs dropped). */
+int iaf_conv3x3_forward_hdet(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, float* h_det, int B, int H, int W,
+                             void* stream);
 /* eps_out with (qz_mean+rz_mean) + exp(qz_logsd+rz_logsd)*eps_out == z: mode "init" of IAFLayer.down runs the posterior
  * block on a PRIOR sample (tf_train.py:60-61, 67-85) */
 int iaf_noise_from_sample(const float* z, const float* qz_mean, const float* qz_logsd, const float* rz_mean,
