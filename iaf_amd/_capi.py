@@ -125,6 +125,10 @@ SIGNATURES = {
     "iaf_stack_get_free_bits_groups": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "iaf_up_iaf2_backward_pre": (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_float] + [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_vp]),
     "iaf_up_iaf2_backward_post": (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_chain_head": (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_chain_tail": (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_chain_backward_pre": (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_float] + [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_chain_backward_post": (ctypes.c_int, [_c_float_p] * 10 + [ctypes.c_int] * 4 + [_vp]),
     "iaf_stack_exchange_errors": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint)]),
     "iaf_stack_range_errors": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint)]),
     "iaf_stack_step_is_f16": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3),

@@ -1,5 +1,5 @@
 // iaf_kernels_objective.hpp -- kernels of the objective side of the model: Gaussian sample / logps, the elementwise halves of the
-// 'up_iaf2_nl' backward, the streaming lower bound, data-dependent init, the discretized logistic, the evaluation tail, and the small
+// 'up_iaf2_nl' backward, the elementwise path of the 'down_iaf2_nl2' chain, the streaming lower bound, data-dependent init, the discretized logistic, the evaluation tail, and the small
 // elementwise ops around them (posterior noise of a sample, KL from its terms, column sums, 2x resampling).
 // Included by iaf_model_ops.hip and by no other unit; the C ABI over these kernels is there.
 #pragma once
@@ -72,6 +72,155 @@ __global__ __launch_bounds__(256) void iaf_up_iaf2_bwd_post_kernel(UpIafBwdP p) 
             const size_t zi = b * nz + (r - nh - nz);
             p.d_uc1[i] = p.dz0[zi] * (p.z0[zi] - p.qz_mean[zi]) - p.Gf[zi];
         } else p.d_uc1[i] = p.dctx[b * nh + (r - nh - 2 * nz)];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// models.cvae_layer with posterior 'down_iaf2_nl2' (models.py:93-98, 272-291, 295-298, 317-318, 454-466): the elementwise path
+// around the chain of two IAF steps, read and written IN PLACE at channel offsets of the two conv outputs
+//   up   [B, 2 n_h + 2 n_z, HW] = [h_det | qz_mean | qz_logsd | up_context]                              (:141-143, 180)
+//   down [B, 2 n_h + 4 n_z, HW] = [h_det | pz_mean | pz_logsd | rz_mean | rz_logsd | down_context]       (:273-279, 296-297)
+// and their gradients in the same layouts.  With mean = qz_mean + rz_mean, lsd = qz_logsd + rz_logsd:
+//   head: z0 = mean + exp(lsd) eps;  logq0 = -(log 2pi + 2 lsd + eps^2) / 2;  context = up_context + down_context
+//   tail: kl = logq0 + s1 + s2 - logp(z2; pz_mean, 2 pz_logsd);  h_out [B, n_h + n_z, HW] = [h_det (down) | z2]
+//   pre:  G = gate[c] * gscale (free bits) or dko[b];  dlt = z2 - pz_mean, e2 = exp(-2 pz_logsd);
+//         dz2 = d_h[z part] + G dlt e2;  d_down[0 : n_h + 2 n_z) = [d_h[h_det part] | -G dlt e2 | G (1 - dlt^2 e2)]
+//   post: dmean = dz0, dlogsd = dz0 (z0 - mean) - G, dcontext = dctx1 + dctx2;
+//         d_up = [d_up_hdet or 0 | dmean | dlogsd | dcontext];  d_down[n_h + 2 n_z : ) = [dmean | dlogsd | dcontext]
+// V = 4: HW % 4 == 0 and every base pointer 16-byte aligned (the entry point checks), so every channel plane starts on a 16-byte
+// boundary and a thread moves four consecutive elements of one plane with one 16-byte access; V = 1: any size, any alignment.
+// Consecutive threads take consecutive units of the output's own index space, so loads and stores of a wave are contiguous except
+// where it straddles a channel-group boundary.
+// ---------------------------------------------------------------------------------------------
+template <int V> struct alignas(4 * V) ChainVec { float v[V]; };
+template <int V> __device__ __forceinline__ ChainVec<V> chain_ld(const float* p) { return *reinterpret_cast<const ChainVec<V>*>(p); }
+template <int V> __device__ __forceinline__ void chain_st(float* p, const ChainVec<V>& x) { *reinterpret_cast<ChainVec<V>*>(p) = x; }
+
+struct ChainP {
+    const float *up, *down, *eps, *logq0, *s1, *s2, *z2, *d_h, *gate, *dko, *z0, *dz0, *G, *dctx1, *dctx2, *d_up;
+    float *o_z0, *o_logq0, *o_context, *o_kl, *o_h, *o_dz2, *o_G, *o_duc1, *o_ddc1;
+    float gscale;
+    int B, n_h, n_z, HW;
+};
+
+template <int V> __global__ __launch_bounds__(256) void iaf_chain_head_kernel(ChainP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per = nz + nh, pu = 2 * nh + 2 * nz, pd = 2 * nh + 4 * nz;
+    const size_t units = (size_t)p.B * per / V;
+    for (size_t u = blockIdx.x * (size_t)blockDim.x + threadIdx.x; u < units; u += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = u * V, b = i / per, r = i - b * per;
+        const float *U = p.up + b * pu, *D = p.down + b * pd;
+        if (r < nz) {
+            const ChainVec<V> qm = chain_ld<V>(U + nh + r), ql = chain_ld<V>(U + nh + nz + r);
+            const ChainVec<V> rm = chain_ld<V>(D + nh + 2 * nz + r), rl = chain_ld<V>(D + nh + 3 * nz + r);
+            const ChainVec<V> e = chain_ld<V>(p.eps + b * nz + r);
+            ChainVec<V> z0, lq;
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const float lsd = ql.v[k] + rl.v[k];
+                z0.v[k] = (qm.v[k] + rm.v[k]) + expf(lsd) * e.v[k];
+                lq.v[k] = -0.5f * (1.8378770664093453f + 2.0f * lsd + e.v[k] * e.v[k]);
+            }
+            chain_st<V>(p.o_z0 + b * nz + r, z0);
+            chain_st<V>(p.o_logq0 + b * nz + r, lq);
+        } else {
+            const size_t e = r - nz;
+            const ChainVec<V> a = chain_ld<V>(U + nh + 2 * nz + e), c = chain_ld<V>(D + nh + 4 * nz + e);
+            ChainVec<V> o;
+#pragma unroll
+            for (int k = 0; k < V; ++k) o.v[k] = a.v[k] + c.v[k];
+            chain_st<V>(p.o_context + b * nh + e, o);
+        }
+    }
+}
+
+template <int V> __global__ __launch_bounds__(256) void iaf_chain_tail_kernel(ChainP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per = nh + nz, pd = 2 * nh + 4 * nz;
+    const size_t units = (size_t)p.B * per / V;
+    for (size_t u = blockIdx.x * (size_t)blockDim.x + threadIdx.x; u < units; u += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = u * V, b = i / per, r = i - b * per;
+        const float* D = p.down + b * pd;
+        if (r < nh) { chain_st<V>(p.o_h + i, chain_ld<V>(D + r)); continue; }             // h_det passes through
+        const size_t e = r - nh, zi = b * nz + e;
+        const ChainVec<V> z = chain_ld<V>(p.z2 + zi), pm = chain_ld<V>(D + nh + e), pl = chain_ld<V>(D + nh + nz + e);
+        const ChainVec<V> lq = chain_ld<V>(p.logq0 + zi), s1 = chain_ld<V>(p.s1 + zi), s2 = chain_ld<V>(p.s2 + zi);
+        ChainVec<V> kl;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const float dlt = z.v[k] - pm.v[k], lv = 2.0f * pl.v[k];
+            const float logp = -0.5f * (1.8378770664093453f + lv + dlt * dlt * expf(-lv));
+            kl.v[k] = ((lq.v[k] + s1.v[k]) + s2.v[k]) - logp;
+        }
+        chain_st<V>(p.o_kl + zi, kl);
+        chain_st<V>(p.o_h + i, z);
+    }
+}
+
+template <int V> __global__ __launch_bounds__(256) void iaf_chain_bwd_pre_kernel(ChainP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per_in = nh + nz, per = nh + 2 * nz, pd = 2 * nh + 4 * nz;
+    const size_t units = (size_t)p.B * per / V;
+    for (size_t u = blockIdx.x * (size_t)blockDim.x + threadIdx.x; u < units; u += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = u * V, b = i / per, r = i - b * per;
+        const float* D = p.down + b * pd;
+        float* O = p.o_ddc1 + b * pd;
+        if (r < nh) { chain_st<V>(O + r, chain_ld<V>(p.d_h + b * per_in + r)); continue; }   // d h_det passes through
+        const bool second = r >= nh + nz;
+        const size_t e = r - nh - (second ? nz : 0), zi = b * nz + e;
+        const float G = p.gate ? p.gate[e / p.HW] * p.gscale : p.dko[b];                   // (a unit never leaves its plane)
+        const ChainVec<V> z = chain_ld<V>(p.z2 + zi), pm = chain_ld<V>(D + nh + e), pl = chain_ld<V>(D + nh + nz + e);
+        ChainVec<V> o;
+        if (!second) {
+            const ChainVec<V> dh = chain_ld<V>(p.d_h + b * per_in + nh + e);
+            ChainVec<V> dz, Gv;
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const float e2 = expf(-2.0f * pl.v[k]), dlt = z.v[k] - pm.v[k];
+                dz.v[k] = dh.v[k] + G * dlt * e2;
+                Gv.v[k] = G;
+                o.v[k] = -G * dlt * e2;
+            }
+            chain_st<V>(p.o_dz2 + zi, dz);
+            chain_st<V>(p.o_G + zi, Gv);
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const float e2 = expf(-2.0f * pl.v[k]), dlt = z.v[k] - pm.v[k];
+                o.v[k] = G * (1.0f - dlt * dlt * e2);
+            }
+        }
+        chain_st<V>(O + r, o);
+    }
+}
+
+template <int V> __global__ __launch_bounds__(256) void iaf_chain_bwd_post_kernel(ChainP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, pu = 2 * nh + 2 * nz, pd = 2 * nh + 4 * nz;
+    const size_t units = (size_t)p.B * pu / V;                       // the index space of d_up_conv1 itself
+    for (size_t u = blockIdx.x * (size_t)blockDim.x + threadIdx.x; u < units; u += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = u * V, b = i / pu, r = i - b * pu;
+        ChainVec<V> o;
+        if (r < nh) {
+            if (p.d_up) o = chain_ld<V>(p.d_up + b * nh + r);
+            else {
+#pragma unroll
+                for (int k = 0; k < V; ++k) o.v[k] = 0.f;
+            }
+            chain_st<V>(p.o_duc1 + i, o);
+            continue;
+        }
+        if (r < nh + nz) o = chain_ld<V>(p.dz0 + b * nz + (r - nh));
+        else if (r < nh + 2 * nz) {
+            const size_t e = r - nh - nz, zi = b * nz + e;
+            const ChainVec<V> dz0 = chain_ld<V>(p.dz0 + zi), z0 = chain_ld<V>(p.z0 + zi), G = chain_ld<V>(p.G + zi);
+            const ChainVec<V> qm = chain_ld<V>(p.up + b * pu + nh + e), rm = chain_ld<V>(p.down + b * pd + nh + 2 * nz + e);
+#pragma unroll
+            for (int k = 0; k < V; ++k) o.v[k] = dz0.v[k] * (z0.v[k] - (qm.v[k] + rm.v[k])) - G.v[k];
+        } else {
+            const size_t ci = b * nh + (r - nh - 2 * nz);
+            const ChainVec<V> a = chain_ld<V>(p.dctx1 + ci), c = chain_ld<V>(p.dctx2 + ci);
+#pragma unroll
+            for (int k = 0; k < V; ++k) o.v[k] = a.v[k] + c.v[k];
+        }
+        chain_st<V>(p.o_duc1 + i, o);
+        chain_st<V>(p.o_ddc1 + b * pd + (nh + 2 * nz) + (r - nh), o);   // the q and the r channels get the same gradient
     }
 }
 

@@ -1,7 +1,7 @@
 // iaf_model_ops.hip -- the operations of the model that take no stack and no conv (C ABI: include/iaf_hip.h): the two ends of the model
 // around the IAFLayer stack (image scaling, x_enc / x_dec and their backward, h_top, obj / loss), the elementwise pieces of the init
-// pass, and the objective side (Gaussian sample / logps, the 'up_iaf2_nl' backward halves, the importance-weighted bound, the
-// evaluation tail, data-dependent init, the likelihood, 2x resampling).
+// pass, and the objective side (Gaussian sample / logps, the 'up_iaf2_nl' backward halves, the elementwise path of the
+// 'down_iaf2_nl2' chain, the importance-weighted bound, the evaluation tail, data-dependent init, the likelihood, 2x resampling).
 // A translation unit of its own beside iaf_engine.hip; its kernel headers are included here and nowhere else.
 // Not here: iaf_kl_free_bits / _gate / _grouped.  They launch iaf_kl_rowsum_kernel and iaf_kl_finish_kernel, which the posterior block
 // of the stack launches too (iaf_kernels_misc.hpp), and a kernel is defined in one unit and launched from that unit only.
@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 
 #include "iaf_hip.h"
 
@@ -275,6 +276,76 @@ extern "C" int iaf_up_iaf2_backward_post(const float* dz0, const float* z0, cons
     hipLaunchKernelGGL(iaf_up_iaf2_bwd_post_kernel, ew_grid((size_t)B * (2 * n_h + 2 * n_z) * HW), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
+
+// The elementwise path of models.cvae_layer 'down_iaf2_nl2' around its two IAF steps (iaf_kernels_objective.hpp: ChainP), in place on
+// the two conv outputs.  The 16-byte form runs only where every plane of every tensor starts on a 16-byte boundary.
+static bool chain_vec4(int HW, std::initializer_list<const void*> ptrs) {
+    if (HW % 4) return false;
+    for (const void* q : ptrs)
+        if ((uintptr_t)q & 15) return false;          // (NULL, an absent optional tensor, passes)
+    return true;
+}
+#define CHAIN_LAUNCH(kernel, vec, n, st, p)                                                                         \
+    do {                                                                                                            \
+        if (vec) hipLaunchKernelGGL(kernel<4>, ew_grid((n) / 4), dim3(256), 0, (hipStream_t)(st), p);               \
+        else hipLaunchKernelGGL(kernel<1>, ew_grid(n), dim3(256), 0, (hipStream_t)(st), p);                         \
+    } while (0)
+
+extern "C" int iaf_chain_head(const float* up_conv1_out, const float* down_conv1_out, const float* eps, float* z0, float* logq0,
+                              float* context, int B, int n_h, int n_z, int HW, void* stream) {
+    if (!up_conv1_out || !down_conv1_out || !eps || !z0 || !logq0 || !context) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    ChainP p;
+    memset(&p, 0, sizeof(p));
+    p.up = up_conv1_out; p.down = down_conv1_out; p.eps = eps; p.o_z0 = z0; p.o_logq0 = logq0; p.o_context = context;
+    p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    const bool vec = chain_vec4(HW, {up_conv1_out, down_conv1_out, eps, z0, logq0, context});
+    CHAIN_LAUNCH(iaf_chain_head_kernel, vec, (size_t)B * ((size_t)n_h + n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_chain_tail(const float* down_conv1_out, const float* logq0, const float* logdet1, const float* logdet2,
+                              const float* z2, float* kl_elem, float* h_out, int B, int n_h, int n_z, int HW, void* stream) {
+    if (!down_conv1_out || !logq0 || !logdet1 || !logdet2 || !z2 || !kl_elem || !h_out) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    ChainP p;
+    memset(&p, 0, sizeof(p));
+    p.down = down_conv1_out; p.logq0 = logq0; p.s1 = logdet1; p.s2 = logdet2; p.z2 = z2; p.o_kl = kl_elem; p.o_h = h_out;
+    p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    const bool vec = chain_vec4(HW, {down_conv1_out, logq0, logdet1, logdet2, z2, kl_elem, h_out});
+    CHAIN_LAUNCH(iaf_chain_tail_kernel, vec, (size_t)B * ((size_t)n_h + n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+
+// gate [n_z] non-NULL: free bits, G = gate[c] * gscale; else G = dko[b] (the convention of iaf_up_iaf2_backward_pre)
+extern "C" int iaf_chain_backward_pre(const float* down_conv1_out, const float* z2, const float* d_h, const float* gate, float gscale,
+                                      const float* dko, float* dz2, float* G, float* d_down_conv1, int B, int n_h, int n_z, int HW,
+                                      void* stream) {
+    if (!down_conv1_out || !z2 || !d_h || !dz2 || !G || !d_down_conv1 || (!gate && !dko)) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    ChainP p;
+    memset(&p, 0, sizeof(p));
+    p.down = down_conv1_out; p.z2 = z2; p.d_h = d_h; p.gate = gate; p.gscale = gscale; p.dko = dko; p.o_dz2 = dz2; p.o_G = G;
+    p.o_ddc1 = d_down_conv1; p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    const bool vec = chain_vec4(HW, {down_conv1_out, z2, d_h, dz2, G, d_down_conv1});
+    CHAIN_LAUNCH(iaf_chain_bwd_pre_kernel, vec, (size_t)B * ((size_t)n_h + 2 * (size_t)n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_chain_backward_post(const float* up_conv1_out, const float* down_conv1_out, const float* z0, const float* dz0,
+                                       const float* G, const float* dctx1, const float* dctx2, const float* d_up, float* d_up_conv1,
+                                       float* d_down_conv1, int B, int n_h, int n_z, int HW, void* stream) {
+    if (!up_conv1_out || !down_conv1_out || !z0 || !dz0 || !G || !dctx1 || !dctx2 || !d_up_conv1 || !d_down_conv1) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    ChainP p;
+    memset(&p, 0, sizeof(p));
+    p.up = up_conv1_out; p.down = down_conv1_out; p.z0 = z0; p.dz0 = dz0; p.G = G; p.dctx1 = dctx1; p.dctx2 = dctx2; p.d_up = d_up;
+    p.o_duc1 = d_up_conv1; p.o_ddc1 = d_down_conv1; p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    const bool vec = chain_vec4(HW, {up_conv1_out, down_conv1_out, z0, dz0, G, dctx1, dctx2, d_up, d_up_conv1, d_down_conv1});
+    CHAIN_LAUNCH(iaf_chain_bwd_post_kernel, vec, (size_t)B * (2 * (size_t)n_h + 2 * (size_t)n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+#undef CHAIN_LAUNCH
 
 extern "C" int iaf_discretized_logistic(const float* mean, const float* logscale, int logscale_is_scalar, const float* sample,
                                         float* out, int B, size_t n_per_row, float binsize, void* stream) {

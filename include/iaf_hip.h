@@ -338,6 +338,33 @@ int iaf_up_iaf2_backward_pre(const float* z, const float* pz_mean, const float* 
                              int B, int n_h, int n_z, int HW, void* stream);
 int iaf_up_iaf2_backward_post(const float* dz0, const float* z0, const float* qz_mean, const float* G, const float* dctx,
                               const float* d_up, float* d_up_conv1, int B, int n_h, int n_z, int HW, void* stream);
+/* The elementwise path of the Theano layer's 'down_iaf2_nl2' posterior -- a chain of two IAF steps, the second with the flipped
+ * ordering, on one context (models.py:93-98, 272-291, 295-298, 317-318, 454-466) -- around the two iaf_step_forward[_train] /
+ * iaf_step_backward calls.  The operands are read, and the gradients written, at channel offsets inside the conv outputs:
+ *   up_conv1_out   [B, 2 n_h + 2 n_z, HW] = [h_det | qz_mean | qz_logsd | up_context]
+ *   down_conv1_out [B, 2 n_h + 4 n_z, HW] = [h_det | pz_mean | pz_logsd | rz_mean | rz_logsd | down_context]
+ * d_up_conv1 / d_down_conv1 have the same layouts.  With mean = qz_mean + rz_mean, lsd = qz_logsd + rz_logsd:
+ *   head: z0 = mean + exp(lsd) eps,  logq0 = -(log 2pi + 2 lsd + eps^2) / 2  (both [B, n_z, HW]),  context = up_context +
+ *         down_context [B, n_h, HW]
+ *   tail: kl_elem = logq0 + logdet1 + logdet2 - logp(z2; pz_mean, 2 pz_logsd) [B, n_z, HW],  h_out [B, n_h + n_z, HW] = [h_det
+ *         (of down_conv1_out) | z2]
+ *   pre:  G = d obj / d kl = gate[c] * gscale (free bits; gate from iaf_kl_free_bits_gate) or dko[b] (gate = NULL), expanded to
+ *         [B, n_z, HW];  dlt = z2 - pz_mean, e2 = exp(-2 pz_logsd);  dz2 = d_h[z part] + G dlt e2;  channels [0, n_h + 2 n_z) of
+ *         d_down_conv1 = [d_h[h_det part] | -G dlt e2 | G (1 - dlt^2 e2)], its other channels are not touched
+ *   post: dmean = dz0, dlogsd = dz0 (z0 - mean) - G, dcontext = dctx1 + dctx2;  d_up_conv1 = [d_up or 0 | dmean | dlogsd |
+ *         dcontext] (d_up [B, n_h, HW] may be NULL);  channels [n_h + 2 n_z, 2 n_h + 4 n_z) of d_down_conv1 = [dmean | dlogsd |
+ *         dcontext], its other channels are not touched
+ * Any positive B, n_h, n_z, HW and any alignment: 16-byte accesses are used only where HW % 4 == 0 and every pointer is 16-byte
+ * aligned.  IAF_ERR_NULL / IAF_ERR_SHAPE come back before any device work. */
+int iaf_chain_head(const float* up_conv1_out, const float* down_conv1_out, const float* eps, float* z0, float* logq0, float* context,
+                   int B, int n_h, int n_z, int HW, void* stream);
+int iaf_chain_tail(const float* down_conv1_out, const float* logq0, const float* logdet1, const float* logdet2, const float* z2,
+                   float* kl_elem, float* h_out, int B, int n_h, int n_z, int HW, void* stream);
+int iaf_chain_backward_pre(const float* down_conv1_out, const float* z2, const float* d_h, const float* gate, float gscale,
+                           const float* dko, float* dz2, float* G, float* d_down_conv1, int B, int n_h, int n_z, int HW, void* stream);
+int iaf_chain_backward_post(const float* up_conv1_out, const float* down_conv1_out, const float* z0, const float* dz0, const float* G,
+                            const float* dctx1, const float* dctx2, const float* d_up, float* d_up_conv1, float* d_down_conv1,
+                            int B, int n_h, int n_z, int HW, void* stream);
 int iaf_kl_combine(const float* logq0, const float* logdet, const float* logp, float* kl, size_t n, void* stream);
 /* out[j] = sum_i mat[i*n + j], i < m: the running `kl_cost += cur_cost` over a model's layers (tf_train.py:198-200) when
  * every layer wrote its [n] KL costs into one row of a [m, n] matrix */
