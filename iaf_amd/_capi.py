@@ -129,6 +129,12 @@ SIGNATURES = {
     "iaf_chain_tail": (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 4 + [_vp]),
     "iaf_chain_backward_pre": (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_float] + [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_vp]),
     "iaf_chain_backward_post": (ctypes.c_int, [_c_float_p] * 10 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_made_head": (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_made_tail": (ctypes.c_int, [_c_float_p] * 9 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_made_backward_pre": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_float] + [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_made_backward_join": (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_made_backward_post": (ctypes.c_int, [_c_float_p] * 10 + [ctypes.c_int] * 4 + [_vp]),
+    "iaf_diag_prior_sample": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 5 + [_vp]),
     "iaf_stack_exchange_errors": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint)]),
     "iaf_stack_range_errors": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint)]),
     "iaf_stack_step_is_f16": (ctypes.c_int, [_vp] + [ctypes.c_int] * 3),

@@ -1,5 +1,5 @@
 // iaf_kernels_objective.hpp -- kernels of the objective side of the model: Gaussian sample / logps, the elementwise halves of the
-// 'up_iaf2_nl' backward, the elementwise path of the 'down_iaf2_nl2' chain, the streaming lower bound, data-dependent init, the discretized logistic, the evaluation tail, and the small
+// 'up_iaf2_nl' backward, the elementwise path of the 'down_iaf2_nl2' chain and of the 'made' prior, the streaming lower bound, data-dependent init, the discretized logistic, the evaluation tail, and the small
 // elementwise ops around them (posterior noise of a sample, KL from its terms, column sums, 2x resampling).
 // Included by iaf_model_ops.hip and by no other unit; the C ABI over these kernels is there.
 #pragma once
@@ -221,6 +221,176 @@ template <int V> __global__ __launch_bounds__(256) void iaf_chain_bwd_post_kerne
         }
         chain_st<V>(p.o_duc1 + i, o);
         chain_st<V>(p.o_ddc1 + b * pd + (nh + 2 * nz) + (r - nh), o);   // the q and the r channels get the same gradient
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// models.cvae_layer with prior 'made' (models.py:36-38, 304-309) and posterior 'down_iaf2_nl' / 'down_iaf2_nl2': the elementwise path
+// around the posterior's one or two IAF steps AND the prior's step, in place on the two conv outputs
+//   up   [B, 2 n_h + 2 n_z, HW] = [h_det | qz_mean | qz_logsd | up_context]
+//   down [B, 3 n_h + 2 n_z, HW] = [h_det | made_context | rz_mean | rz_logsd | down_context]               (:38, 273-279, 305)
+// With (u, s_p) = the prior stack's step on (z, made_context), i.e. u = (z - 0.1 m) / exp(0.1 s), s_p = 0.1 s:
+//   logps = -(log 2pi) / 2 - s_p - u^2 / 2                                                                 (:306-309)
+//   head: z0, logq0, context as iaf_chain_head_kernel;  made_context [B, n_h, HW] = the contiguous copy the prior stack reads
+//   tail: kl = ((logq0 + s1) [+ s2]) + ((log 2pi) / 2 + s_p + u^2 / 2);  h_out = [h_det | z];  kl == NULL: only h_out
+//   pre:  G = gate[c] * gscale (free bits) or dko[b];  du = G u;  d_down[h_det part] = d_h[h_det part]
+//   join: dz = d_h[z part] + dz_p;  d_down[made_context part] = d_made_context
+//   post: as iaf_chain_bwd_post_kernel at this layout's offsets, dctx2 optional (one flow)
+// diag prior, any diag layout (n_down channels, [h_det | pz_mean | pz_logsd | ...]):  h_out = [h_det | pz_mean + eps exp(pz_logsd)]
+// V as for the chain; a unit never leaves its channel plane.
+// ---------------------------------------------------------------------------------------------
+struct MadeP {
+    const float *up, *down, *eps, *logq0, *s1, *s2, *z, *u, *s_p, *d_h, *gate, *dko, *dz_p, *d_mctx, *z0, *dz0, *G, *dctx1, *dctx2, *d_up;
+    float *o_z0, *o_logq0, *o_context, *o_mctx, *o_kl, *o_h, *o_du, *o_G, *o_dz, *o_duc1, *o_ddc1;
+    float gscale;
+    int B, n_h, n_z, HW, n_down;
+};
+
+template <int V> __global__ __launch_bounds__(256) void iaf_made_head_kernel(MadeP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per = nz + 2 * nh, pu = 2 * nh + 2 * nz, pd = 3 * nh + 2 * nz;
+    const size_t units = (size_t)p.B * per / V;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < units; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = t * V, b = i / per, r = i - b * per;
+        const float *U = p.up + b * pu, *D = p.down + b * pd;
+        if (r < nz) {
+            const ChainVec<V> qm = chain_ld<V>(U + nh + r), ql = chain_ld<V>(U + nh + nz + r);
+            const ChainVec<V> rm = chain_ld<V>(D + 2 * nh + r), rl = chain_ld<V>(D + 2 * nh + nz + r);
+            const ChainVec<V> e = chain_ld<V>(p.eps + b * nz + r);
+            ChainVec<V> z0, lq;
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const float lsd = ql.v[k] + rl.v[k];
+                z0.v[k] = (qm.v[k] + rm.v[k]) + expf(lsd) * e.v[k];
+                lq.v[k] = -0.5f * (1.8378770664093453f + 2.0f * lsd + e.v[k] * e.v[k]);
+            }
+            chain_st<V>(p.o_z0 + b * nz + r, z0);
+            chain_st<V>(p.o_logq0 + b * nz + r, lq);
+        } else if (r < nz + nh) {
+            const size_t e = r - nz;
+            const ChainVec<V> a = chain_ld<V>(U + nh + 2 * nz + e), c = chain_ld<V>(D + 2 * nh + 2 * nz + e);
+            ChainVec<V> o;
+#pragma unroll
+            for (int k = 0; k < V; ++k) o.v[k] = a.v[k] + c.v[k];
+            chain_st<V>(p.o_context + b * nh + e, o);
+        } else {
+            const size_t e = r - nz - nh;
+            chain_st<V>(p.o_mctx + b * nh + e, chain_ld<V>(D + nh + e));
+        }
+    }
+}
+
+template <int V> __global__ __launch_bounds__(256) void iaf_made_tail_kernel(MadeP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per = nh + nz, pd = 3 * nh + 2 * nz;
+    const size_t units = (size_t)p.B * per / V;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < units; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = t * V, b = i / per, r = i - b * per;
+        if (r < nh) { chain_st<V>(p.o_h + i, chain_ld<V>(p.down + b * pd + r)); continue; }   // h_det passes through
+        const size_t zi = b * nz + (r - nh);
+        chain_st<V>(p.o_h + i, chain_ld<V>(p.z + zi));
+        if (!p.o_kl) continue;                                                               // the pack alone (down_p)
+        const ChainVec<V> lq = chain_ld<V>(p.logq0 + zi), s1 = chain_ld<V>(p.s1 + zi), u = chain_ld<V>(p.u + zi), sp = chain_ld<V>(p.s_p + zi);
+        ChainVec<V> kl;
+        if (p.s2) {
+            const ChainVec<V> s2 = chain_ld<V>(p.s2 + zi);
+#pragma unroll
+            for (int k = 0; k < V; ++k) kl.v[k] = (lq.v[k] + s1.v[k]) + s2.v[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; ++k) kl.v[k] = lq.v[k] + s1.v[k];
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) kl.v[k] += (0.9189385332046727f + sp.v[k]) + 0.5f * u.v[k] * u.v[k];
+        chain_st<V>(p.o_kl + zi, kl);
+    }
+}
+
+template <int V> __global__ __launch_bounds__(256) void iaf_made_bwd_pre_kernel(MadeP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per = nh + nz, pd = 3 * nh + 2 * nz;
+    const size_t units = (size_t)p.B * per / V;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < units; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = t * V, b = i / per, r = i - b * per;
+        if (r < nh) { chain_st<V>(p.o_ddc1 + b * pd + r, chain_ld<V>(p.d_h + i)); continue; }   // d h_det passes through
+        const size_t e = r - nh, zi = b * nz + e;
+        const float G = p.gate ? p.gate[e / p.HW] * p.gscale : p.dko[b];                      // (a unit never leaves its plane)
+        const ChainVec<V> u = chain_ld<V>(p.u + zi);
+        ChainVec<V> du, Gv;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            du.v[k] = G * u.v[k];
+            Gv.v[k] = G;
+        }
+        chain_st<V>(p.o_du + zi, du);
+        chain_st<V>(p.o_G + zi, Gv);
+    }
+}
+
+template <int V> __global__ __launch_bounds__(256) void iaf_made_bwd_join_kernel(MadeP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per = nz + nh, pd = 3 * nh + 2 * nz;
+    const size_t units = (size_t)p.B * per / V;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < units; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = t * V, b = i / per, r = i - b * per;
+        if (r < nz) {
+            const ChainVec<V> a = chain_ld<V>(p.d_h + b * per + nh + r), c = chain_ld<V>(p.dz_p + b * nz + r);
+            ChainVec<V> o;
+#pragma unroll
+            for (int k = 0; k < V; ++k) o.v[k] = a.v[k] + c.v[k];
+            chain_st<V>(p.o_dz + b * nz + r, o);
+        } else {
+            const size_t e = r - nz;
+            chain_st<V>(p.o_ddc1 + b * pd + nh + e, chain_ld<V>(p.d_mctx + b * nh + e));
+        }
+    }
+}
+
+template <int V> __global__ __launch_bounds__(256) void iaf_made_bwd_post_kernel(MadeP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, pu = 2 * nh + 2 * nz, pd = 3 * nh + 2 * nz;
+    const size_t units = (size_t)p.B * pu / V;                       // the index space of d_up_conv1 itself
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < units; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = t * V, b = i / pu, r = i - b * pu;
+        ChainVec<V> o;
+        if (r < nh) {
+            if (p.d_up) o = chain_ld<V>(p.d_up + b * nh + r);
+            else {
+#pragma unroll
+                for (int k = 0; k < V; ++k) o.v[k] = 0.f;
+            }
+            chain_st<V>(p.o_duc1 + i, o);
+            continue;
+        }
+        if (r < nh + nz) o = chain_ld<V>(p.dz0 + b * nz + (r - nh));
+        else if (r < nh + 2 * nz) {
+            const size_t e = r - nh - nz, zi = b * nz + e;
+            const ChainVec<V> dz0 = chain_ld<V>(p.dz0 + zi), z0 = chain_ld<V>(p.z0 + zi), G = chain_ld<V>(p.G + zi);
+            const ChainVec<V> qm = chain_ld<V>(p.up + b * pu + nh + e), rm = chain_ld<V>(p.down + b * pd + 2 * nh + e);
+#pragma unroll
+            for (int k = 0; k < V; ++k) o.v[k] = dz0.v[k] * (z0.v[k] - (qm.v[k] + rm.v[k])) - G.v[k];
+        } else {
+            const size_t ci = b * nh + (r - nh - 2 * nz);
+            o = chain_ld<V>(p.dctx1 + ci);
+            if (p.dctx2) {
+                const ChainVec<V> c = chain_ld<V>(p.dctx2 + ci);
+#pragma unroll
+                for (int k = 0; k < V; ++k) o.v[k] += c.v[k];
+            }
+        }
+        chain_st<V>(p.o_duc1 + i, o);
+        chain_st<V>(p.o_ddc1 + b * pd + 2 * nh + (r - nh), o);          // the q and the r channels get the same gradient
+    }
+}
+
+template <int V> __global__ __launch_bounds__(256) void iaf_diag_prior_sample_kernel(MadeP p) {
+    const size_t nh = (size_t)p.n_h * p.HW, nz = (size_t)p.n_z * p.HW, per = nh + nz, pd = (size_t)p.n_down * p.HW;
+    const size_t units = (size_t)p.B * per / V;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < units; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = t * V, b = i / per, r = i - b * per;
+        const float* D = p.down + b * pd;
+        if (r < nh) { chain_st<V>(p.o_h + i, chain_ld<V>(D + r)); continue; }                // h_det passes through
+        const size_t e = r - nh;
+        const ChainVec<V> pm = chain_ld<V>(D + nh + e), pl = chain_ld<V>(D + nh + nz + e), ep = chain_ld<V>(p.eps + b * nz + e);
+        ChainVec<V> o;
+#pragma unroll
+        for (int k = 0; k < V; ++k) o.v[k] = pm.v[k] + ep.v[k] * expf(pl.v[k]);
+        chain_st<V>(p.o_h + i, o);
     }
 }
 

@@ -1,7 +1,7 @@
 // iaf_model_ops.hip -- the operations of the model that take no stack and no conv (C ABI: include/iaf_hip.h): the two ends of the model
 // around the IAFLayer stack (image scaling, x_enc / x_dec and their backward, h_top, obj / loss), the elementwise pieces of the init
 // pass, and the objective side (Gaussian sample / logps, the 'up_iaf2_nl' backward halves, the elementwise path of the
-// 'down_iaf2_nl2' chain, the importance-weighted bound, the evaluation tail, data-dependent init, the likelihood, 2x resampling).
+// 'down_iaf2_nl2' chain and of the 'made' prior, the importance-weighted bound, the evaluation tail, data-dependent init, the likelihood, 2x resampling).
 // A translation unit of its own beside iaf_engine.hip; its kernel headers are included here and nowhere else.
 // Not here: iaf_kl_free_bits / _gate / _grouped.  They launch iaf_kl_rowsum_kernel and iaf_kl_finish_kernel, which the posterior block
 // of the stack launches too (iaf_kernels_misc.hpp), and a kernel is defined in one unit and launched from that unit only.
@@ -343,6 +343,92 @@ extern "C" int iaf_chain_backward_post(const float* up_conv1_out, const float* d
     p.o_duc1 = d_up_conv1; p.o_ddc1 = d_down_conv1; p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
     const bool vec = chain_vec4(HW, {up_conv1_out, down_conv1_out, z0, dz0, G, dctx1, dctx2, d_up, d_up_conv1, d_down_conv1});
     CHAIN_LAUNCH(iaf_chain_bwd_post_kernel, vec, (size_t)B * (2 * (size_t)n_h + 2 * (size_t)n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+// The elementwise path of models.cvae_layer with prior 'made' around the posterior's steps and the prior's step (iaf_kernels_objective.hpp:
+// MadeP), in place on the two conv outputs; down_conv1_out has 3 n_h + 2 n_z channels here.
+extern "C" int iaf_made_head(const float* up_conv1_out, const float* down_conv1_out, const float* eps, float* z0, float* logq0,
+                             float* context, float* made_context, int B, int n_h, int n_z, int HW, void* stream) {
+    if (!up_conv1_out || !down_conv1_out || !eps || !z0 || !logq0 || !context || !made_context) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    MadeP p;
+    memset(&p, 0, sizeof(p));
+    p.up = up_conv1_out; p.down = down_conv1_out; p.eps = eps; p.o_z0 = z0; p.o_logq0 = logq0; p.o_context = context;
+    p.o_mctx = made_context; p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    const bool vec = chain_vec4(HW, {up_conv1_out, down_conv1_out, eps, z0, logq0, context, made_context});
+    CHAIN_LAUNCH(iaf_made_head_kernel, vec, (size_t)B * (2 * (size_t)n_h + n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+
+// kl_elem NULL: only h_out = [h_det | z] is written, and logq0, logdet1, u, s_p may be NULL; logdet2 NULL: one posterior flow
+extern "C" int iaf_made_tail(const float* down_conv1_out, const float* logq0, const float* logdet1, const float* logdet2, const float* z,
+                             const float* u, const float* s_p, float* kl_elem, float* h_out, int B, int n_h, int n_z, int HW,
+                             void* stream) {
+    if (!down_conv1_out || !z || !h_out || (kl_elem && (!logq0 || !logdet1 || !u || !s_p))) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    MadeP p;
+    memset(&p, 0, sizeof(p));
+    p.down = down_conv1_out; p.z = z; p.o_h = h_out; p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    bool vec = chain_vec4(HW, {down_conv1_out, z, h_out});
+    if (kl_elem) {
+        p.logq0 = logq0; p.s1 = logdet1; p.s2 = logdet2; p.u = u; p.s_p = s_p; p.o_kl = kl_elem;
+        vec = vec && chain_vec4(HW, {logq0, logdet1, logdet2, u, s_p, kl_elem});
+    }
+    CHAIN_LAUNCH(iaf_made_tail_kernel, vec, (size_t)B * ((size_t)n_h + n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+
+// gate [n_z] non-NULL: free bits, G = gate[c] * gscale; else G = dko[b] (the convention of iaf_chain_backward_pre)
+extern "C" int iaf_made_backward_pre(const float* u, const float* d_h, const float* gate, float gscale, const float* dko, float* du,
+                                     float* G, float* d_down_conv1, int B, int n_h, int n_z, int HW, void* stream) {
+    if (!u || !d_h || !du || !G || !d_down_conv1 || (!gate && !dko)) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    MadeP p;
+    memset(&p, 0, sizeof(p));
+    p.u = u; p.d_h = d_h; p.gate = gate; p.gscale = gscale; p.dko = dko; p.o_du = du; p.o_G = G; p.o_ddc1 = d_down_conv1;
+    p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    const bool vec = chain_vec4(HW, {u, d_h, du, G, d_down_conv1});
+    CHAIN_LAUNCH(iaf_made_bwd_pre_kernel, vec, (size_t)B * ((size_t)n_h + n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_made_backward_join(const float* d_h, const float* dz_p, const float* d_made_context, float* dz, float* d_down_conv1,
+                                      int B, int n_h, int n_z, int HW, void* stream) {
+    if (!d_h || !dz_p || !d_made_context || !dz || !d_down_conv1) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    MadeP p;
+    memset(&p, 0, sizeof(p));
+    p.d_h = d_h; p.dz_p = dz_p; p.d_mctx = d_made_context; p.o_dz = dz; p.o_ddc1 = d_down_conv1;
+    p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    const bool vec = chain_vec4(HW, {d_h, dz_p, d_made_context, dz, d_down_conv1});
+    CHAIN_LAUNCH(iaf_made_bwd_join_kernel, vec, (size_t)B * ((size_t)n_h + n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int iaf_made_backward_post(const float* up_conv1_out, const float* down_conv1_out, const float* z0, const float* dz0,
+                                      const float* G, const float* dctx1, const float* dctx2, const float* d_up, float* d_up_conv1,
+                                      float* d_down_conv1, int B, int n_h, int n_z, int HW, void* stream) {
+    if (!up_conv1_out || !down_conv1_out || !z0 || !dz0 || !G || !dctx1 || !d_up_conv1 || !d_down_conv1) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0) return IAF_ERR_SHAPE;
+    MadeP p;
+    memset(&p, 0, sizeof(p));
+    p.up = up_conv1_out; p.down = down_conv1_out; p.z0 = z0; p.dz0 = dz0; p.G = G; p.dctx1 = dctx1; p.dctx2 = dctx2; p.d_up = d_up;
+    p.o_duc1 = d_up_conv1; p.o_ddc1 = d_down_conv1; p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW;
+    const bool vec = chain_vec4(HW, {up_conv1_out, down_conv1_out, z0, dz0, G, dctx1, dctx2, d_up, d_up_conv1, d_down_conv1});
+    CHAIN_LAUNCH(iaf_made_bwd_post_kernel, vec, (size_t)B * (2 * (size_t)n_h + 2 * (size_t)n_z) * HW, stream, p);
+    return (int)hipGetLastError();
+}
+
+// down_p with the diag prior: down_conv1_out [B, n_down, HW] in any diag layout, n_down >= n_h + 2 n_z
+extern "C" int iaf_diag_prior_sample(const float* down_conv1_out, const float* eps, float* h_out, int B, int n_down, int n_h, int n_z,
+                                     int HW, void* stream) {
+    if (!down_conv1_out || !eps || !h_out) return IAF_ERR_NULL;
+    if (B <= 0 || n_h <= 0 || n_z <= 0 || HW <= 0 || (long long)n_down < (long long)n_h + 2LL * n_z) return IAF_ERR_SHAPE;
+    MadeP p;
+    memset(&p, 0, sizeof(p));
+    p.down = down_conv1_out; p.eps = eps; p.o_h = h_out; p.B = B; p.n_h = n_h; p.n_z = n_z; p.HW = HW; p.n_down = n_down;
+    const bool vec = chain_vec4(HW, {down_conv1_out, eps, h_out});
+    CHAIN_LAUNCH(iaf_diag_prior_sample_kernel, vec, (size_t)B * ((size_t)n_h + n_z) * HW, stream, p);
     return (int)hipGetLastError();
 }
 #undef CHAIN_LAUNCH

@@ -8,6 +8,7 @@ with V in HWIO [3,3,n_in,n_out] fp32 (layers.py:35,53-55).
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -973,6 +974,146 @@ def kl_free_bits(kl, kl_min, want_gate=False, groups=1):
     _capi.check(_capi.lib().iaf_kl_free_bits(_ptr(kl), _ptr(kl_obj), _ptr(kl_cost), B, C, H * W, float(kl_min), _ptr(scratch),
                                              _stream()))
     return kl_cost, kl_obj
+
+
+class EmbeddedTheanoStack(object):
+    """A Theano-statement stack with the plain ordering whose channel counts are NOT multiples of 16 (which is all the engine states
+    that operator for), run EMBEDDED in an ARStack t = 16 / gcd(16, n_z, n_h) times as wide: channel c sits at position t c, everything
+    else is zero.  Needs n_z | n_h.  The masks of the wide stack (ar.py:243-264) restricted to these positions are the narrow stack's
+    own (out channel j of a hidden conv sees in channel c iff c <= j // k on both sides, of an output conv iff c < k j), the zero rows
+    and columns add nothing to a sum or to a kernel's l2 norm, and a zero z channel stays zero (m = s = 0): the same function, and so
+    the same gradients at the real entries (tests/test_made_reference.py shows it on the NumPy statement).  The flipped ordering and
+    n_z > n_h do not embed this way.
+
+    The object owns the wide stack (`wide`) and offers ONLY what is listed here, with the narrow stack's tensors and parameter dicts:
+    prepare, set_training, ar_multiconv2d, iaf_step, iaf_step_train, iaf_step_backward, iaf_step_inverse, iaf_step_inverse_queued.
+    Tuning, precision and timing calls go to `wide` directly, in the wide stack's own sizes.  Every call pads its activations with
+    torch (a zero fill and a strided copy each) and slices the results: stream-ordered and capturable, but not free.  PrepBatch takes
+    it like an ARStack (through `_h` and `_param_tensors`)."""
+
+    def __init__(self, n_z, n_h, variant=_capi.IAF_VARIANT_THEANO):
+        n_h = list(n_h)
+        if variant not in ("theano", _capi.IAF_VARIANT_THEANO):
+            raise _capi.UnsupportedError("only the plain Theano ordering embeds in a wider stack")
+        if not n_h or len(set(n_h)) > 1 or n_h[0] % n_z:
+            raise _capi.UnsupportedError("an embedded Theano stack needs equal hidden sizes that are multiples of n_z, got n_z = %d, "
+                                         "n_h = %r" % (n_z, n_h))
+        self.n_z, self.n_h, self.n_h_list, self.depth_ar = int(n_z), int(n_h[0]), n_h, len(n_h)
+        self.variant = _capi.IAF_VARIANT_THEANO
+        self.t = 16 // math.gcd(16, math.gcd(self.n_z, self.n_h))
+        self.wide = ARStack(self.n_z * self.t, [self.n_h * self.t] * self.depth_ar, variant=self.variant)
+        self._h = self.wide._h                  # (PrepBatch reads the engine handle; the wide stack owns it)
+        self._wide_cache = None                 # (key, the caller's tensors -- kept alive, so no address is reused --, wide params)
+
+    # -- narrow <-> wide ---------------------------------------------------------------------------
+    def _widen(self, x, channels, name):
+        if x is None:
+            return None
+        _check_act(x, name)
+        if x.dim() != 4 or x.shape[1] != channels:
+            raise ValueError("%s must be [B, %d, H, W], got %s" % (name, channels, tuple(x.shape)))
+        out = torch.zeros(x.shape[0], channels * self.t, x.shape[2], x.shape[3], dtype=torch.float32, device=x.device)
+        out[:, ::self.t] = x
+        return out
+
+    def _narrow(self, x):
+        return None if x is None else x[:, ::self.t].contiguous()
+
+    def _in_index(self, w_wide):
+        """positions of the narrow conv's input channels in the wide weight's axis 1: t c, and the border-indicator channel, last"""
+        n = w_wide.shape[1] - 1
+        return torch.cat([torch.arange(0, n, self.t, device=w_wide.device), torch.tensor([n], device=w_wide.device)])
+
+    def wide_params(self, params):
+        """the params dict of the wide stack: every w at rows t j and columns _in_index, every s and b at positions t j (cached until
+        a tensor is replaced or modified in place)"""
+        keys = [k for ks in self.wide._grad_keys() for k in ks]
+        src = [params[k] for k in keys]
+        key = tuple((p.data_ptr(), p._version) for p in src)
+        if self._wide_cache is None or key != self._wide_cache[0]:
+            t, sizes, wide = self.t, [self.n_z] + self.n_h_list, {}
+            for k, p in zip(keys, src):
+                conv = k.rsplit("_", 1)[0]
+                n_out = self.n_z if conv.startswith("out_") else sizes[int(conv) + 1]
+                n_in = sizes[-1] if conv.startswith("out_") else sizes[int(conv)]
+                if k.endswith("_w"):
+                    _check_act(p, k, (n_out, n_in + 1, 3, 3))
+                    w = torch.zeros(n_out * t, n_in * t + 1, 3, 3, dtype=torch.float32, device=p.device)
+                    rows = torch.arange(0, n_out * t, t, device=p.device)
+                    w[rows[:, None], self._in_index(w)[None, :]] = p
+                else:
+                    _check_act(p, k, (n_out,))
+                    w = torch.zeros(n_out * t, dtype=torch.float32, device=p.device)
+                    w[::t] = p
+                wide[k] = w
+            self._wide_cache = (key, src, wide)
+        return self._wide_cache[2]
+
+    def _param_tensors(self, params):
+        return self.wide._param_tensors(self.wide_params(params))
+
+    # -- what the narrow stack offers -----------------------------------------------------------------
+    def prepare(self, params, force=False):
+        self.wide.prepare(self.wide_params(params), force=force)
+
+    def set_training(self, on=True):
+        self.wide.set_training(on)
+
+    @property
+    def _prep_key(self):
+        """the wide stack's prepare cache (PrepBatch clears it after a batched prep)"""
+        return self.wide._prep_key
+
+    @_prep_key.setter
+    def _prep_key(self, v):
+        self.wide._prep_key = v
+
+    def _run(self, method, z, context, out, **kw):
+        """`method` of the wide stack on the widened activations; its first two results are activations and come back narrow (into
+        `out` where the caller gave it), what follows them (sweeps, residual) as it is"""
+        if out is not None:
+            for o in out:
+                _check_act(o, "out", z.shape)
+        res = getattr(self.wide, method)(self._widen(z, self.n_z, "z"), self._widen(context, self.n_h, "context"), **kw)
+        narrow = [self._narrow(r) for r in res[:2]]
+        if out is not None:
+            for o, r in zip(out, narrow):
+                o.copy_(r)
+            narrow = list(out)
+        return type(res)(narrow + list(res[2:]))
+
+    def ar_multiconv2d(self, z, context, out=None):
+        return self._run("ar_multiconv2d", z, context, out)
+
+    def iaf_step(self, z, context, out=None):
+        return self._run("iaf_step", z, context, out)
+
+    def iaf_step_train(self, z, context):
+        return self._run("iaf_step_train", z, context, None)
+
+    def iaf_step_inverse(self, z, context, max_sweeps=64, tol=1e-6, check_every=4, out=None):
+        return self._run("iaf_step_inverse", z, context, out, max_sweeps=max_sweeps, tol=tol, check_every=check_every)
+
+    def iaf_step_inverse_queued(self, z, context, max_sweeps=64, tol=1e-6, check_every=4, out=None, stats=None):
+        return self._run("iaf_step_inverse_queued", z, context, out, max_sweeps=max_sweeps, tol=tol, check_every=check_every, stats=stats)
+
+    def iaf_step_backward(self, z, context, z_new, logsd, dz_new, dlogsd, params):
+        acts = [self._widen(z, self.n_z, "z"), self._widen(context, self.n_h, "context")]
+        acts += [self._widen(x, self.n_z, nm) for nm, x in (("z_new", z_new), ("logsd", logsd), ("dz_new", dz_new), ("dlogsd", dlogsd))]
+        dz, dctx, grads = self.wide.iaf_step_backward(*acts, self.wide_params(params))
+        t = self.t
+        return self._narrow(dz), self._narrow(dctx), {
+            k: (g[::t][:, self._in_index(g)] if k.endswith("_w") else g[::t]).contiguous() for k, g in grads.items()}
+
+
+def theano_stack(n_z, n_h, variant, embed=False):
+    """the ARStack of a Theano multiconv2d; with embed=True an EmbeddedTheanoStack where the plain ordering meets channel counts that
+    are not multiples of 16 (n_z | n_h) -- anything else is the ARStack, which raises for what the engine does not cover"""
+    n_h = list(n_h)
+    if (embed and variant == _capi.IAF_VARIANT_THEANO and n_h and len(set(n_h)) == 1 and (n_z % 16 or n_h[0] % 16)
+            and n_h[0] % n_z == 0):
+        return EmbeddedTheanoStack(n_z, n_h, variant)
+    return ARStack(n_z, n_h, variant=variant)
 
 
 class PrepBatch(object):

@@ -1,7 +1,7 @@
-"""The IAF part of the reference's Theano layer, models.cvae_layer (models.py:14-345), prior 'diag', for the two posteriors BASELINE
-names -- 'down_iaf2_nl' (configs 0-2, 4) and 'up_iaf2_nl' (config 3) -- and for 'down_iaf2_nl2' (models.py:93-98, 272-291): a CHAIN of two
-IAF steps on one context, posterior_conv1 with the plain ordering and posterior_conv2 with the flipped one, both log-determinants added
-to logqs -- the construction of the IAF paper, in which no latent stays first in every ordering.
+"""The IAF part of the reference's Theano layer, models.cvae_layer (models.py:14-345), priors 'diag' and 'made', for the two posteriors
+BASELINE names -- 'down_iaf2_nl' (configs 0-2, 4) and 'up_iaf2_nl' (config 3) -- and for 'down_iaf2_nl2' (models.py:93-98, 272-291): a CHAIN
+of two IAF steps on one context, posterior_conv1 with the plain ordering and posterior_conv2 with the flipped one, both log-determinants
+added to logqs -- the construction of the IAF paper, in which no latent stays first in every ordering.
 
 Boundary: the plain Theano convs around the IAF step (up_conv1/2, down_conv1/2: graphy/nodes/conv.py) are out
 of scope; this wrapper takes THEIR OUTPUTS in the reference's channel order and returns what the next conv consumes:
@@ -16,6 +16,22 @@ context, the KL, concat([h_det, z]), and the two elementwise halves of the backw
 _backward_pre / _backward_post) that read their operands at channel offsets INSIDE the two conv outputs and write the gradients of the
 conv outputs whole: no split() copies, no torch.cat.
 
+prior='made' (models.py:36-38, 304-309; with 'down_iaf2_nl' and 'down_iaf2_nl2') is the autoregressive prior: a further stack,
+<name>_prior_conv1 with the plain ordering, reads z and a context of its own, and down_conv1 emits that context in place of the prior's
+mean and log standard deviation:
+
+    up_conv1 output    [h_det (n_h) | qz_mean (n_z) | qz_logsd (n_z) | up_context (n_h)]                         unchanged
+    down_conv1 output  [h_det (n_h) | made_context (n_h) | rz_mean (n_z) | rz_logsd (n_z) | down_context (n_h)]   :38, 273-279, 305
+
+With (u, s_p) = prior_stack.iaf_step(z, made_context) the prior's density is logps = -(log 2pi)/2 - s_p - u^2/2, so the density is one
+more launch of the step kernels and its gradient one more iaf_step_backward; iaf_made_head / _tail / _backward_pre / _backward_join /
+_backward_post are the elementwise launches around the steps.  down_p() (models.py:330-359) samples the prior: the reference leaves
+z = eps for 'made' (:338-340); exact=True solves z = 0.1 m(z) + exp(0.1 s(z)) eps with the stack's inverse step, the ancestral sample.
+The engine states the Theano operator for channel counts that are multiples of 16; with prior 'made' the plain-ordering stacks (the
+prior's, and the posterior's first unless flipmask) of a layer with smaller counts and n_z | n_h run embedded in wider ones
+(layers.EmbeddedTheanoStack): the same values and gradients, at the price of torch pad and slice copies around every step.  The flipped
+ordering does not embed, so flipmask=True and 'down_iaf2_nl2' stay UnsupportedError at such sizes.
+
 The masked-AR convs run on the GPU through the Theano statement of the operator (IAF_VARIANT_THEANO[_FLIPMASK]); the free
 bits follow models.py:454-466 (a SCALAR per layer: sum over channels of max(kl_min, batch-mean of the per-channel KL))."""
 import ctypes
@@ -25,29 +41,44 @@ import torch
 from . import _capi
 from .distributions import gaussian_diag_logps_logsd
 from .iaf_layer import gaussian_sample
-from .layers import ARStack, PrepBatch, kl_free_bits, split, _check_act, _ptr, _stream
+from .layers import ARStack, PrepBatch, kl_free_bits, split, theano_stack, _check_act, _ptr, _stream
 
 POSTERIORS = ("down_iaf2_nl", "up_iaf2_nl", "down_iaf2_nl2")
+PRIORS = ("diag", "made")
 
 
 class CVAELayerIAF(object):
-    def __init__(self, name, n_h, n_z, depth_ar, posterior="down_iaf2_nl", flipmask=False, kl_min=0.0):
+    def __init__(self, name, n_h, n_z, depth_ar, posterior="down_iaf2_nl", flipmask=False, kl_min=0.0, prior="diag"):
+        if prior not in PRIORS:
+            raise Exception("Unknown prior")                                      # models.py:43
         if posterior not in POSTERIORS:
             raise Exception("Unknown posterior " + posterior)                     # models.py:115
+        if prior == "made" and posterior == "up_iaf2_nl":
+            raise ValueError("prior 'made' with posterior 'up_iaf2_nl' is not built: use 'down_iaf2_nl' or 'down_iaf2_nl2'")
         self.name, self.n_h, self.n_z, self.depth_ar = name, int(n_h), int(n_z), int(depth_ar)
-        self.posterior, self.kl_min = posterior, float(kl_min)
-        self.stack = ARStack(self.n_z, [self.n_h] * self.depth_ar,
-                             variant=_capi.IAF_VARIANT_THEANO_FLIPMASK if flipmask else _capi.IAF_VARIANT_THEANO)
+        self.posterior, self.kl_min, self.prior = posterior, float(kl_min), prior
+        # With prior 'made', BOTH plain-ordering stacks (this one unless flipmask, and the prior's) may have channel counts that are not
+        # multiples of 16 (n_z | n_h): theano_stack then returns an EmbeddedTheanoStack, which pads and slices with torch around
+        # every step.  The flipped ordering does not embed: flipmask=True and 'down_iaf2_nl2' raise UnsupportedError at such sizes.
+        self.stack = theano_stack(self.n_z, [self.n_h] * self.depth_ar,
+                                  _capi.IAF_VARIANT_THEANO_FLIPMASK if flipmask else _capi.IAF_VARIANT_THEANO, embed=(prior == "made"))
         # the second flow of the chain is ALWAYS flipped (models.py:98 hard-codes True); `flipmask` is the first flow's
         self.stack2, self._prep = None, None
         if posterior == "down_iaf2_nl2":
             if self.depth_ar < 1:
                 raise ValueError("'down_iaf2_nl2' needs depth_ar >= 1: both flows take the context through their first conv")
             self.stack2 = ARStack(self.n_z, [self.n_h] * self.depth_ar, variant=_capi.IAF_VARIANT_THEANO_FLIPMASK)
+        # the MADE prior's stack always has the plain ordering (models.py:37 hard-codes False)
+        self.prior_stack = None
+        if prior == "made":
+            if self.depth_ar < 1:
+                raise ValueError("prior 'made' needs depth_ar >= 1: the prior's stack takes made_context through its first conv")
+            self.prior_stack = theano_stack(self.n_z, [self.n_h] * self.depth_ar, _capi.IAF_VARIANT_THEANO, embed=True)
         self._st = None
         self.training = False
         self._rel = None
         self._rel2 = None
+        self._rel_p = None
 
     def set_training(self, on=True):
         """keep what backward() needs in up() / down_q() (call load() again afterwards: the data-gradient weight packs are
@@ -55,27 +86,39 @@ class CVAELayerIAF(object):
         self.stack.set_training(on)
         if self.stack2 is not None:
             self.stack2.set_training(on)
+        if self.prior_stack is not None:
+            self.prior_stack.set_training(on)
         self.training = bool(on)
 
     def load(self, w):
         """w: the reference's parameter dict; reads w[name + '_posterior_conv1_<i>_w|_b|_s'] and '..._out_<i>_...', for
-        'down_iaf2_nl2' also w[name + '_posterior_conv2_...'] (both stacks prepared in ONE launch)"""
+        'down_iaf2_nl2' also w[name + '_posterior_conv2_...'], for prior 'made' also w[name + '_prior_conv1_...'] (all stacks
+        prepared in ONE launch)"""
         pre = self.name + "_posterior_conv1_"
         self._rel = {k[len(pre):]: v for k, v in w.items() if k.startswith(pre)}
-        if self.stack2 is None:
+        if self.stack2 is None and self.prior_stack is None:
             self.stack.prepare(self._rel)
             return
-        pre2 = self.name + "_posterior_conv2_"
-        self._rel2 = {k[len(pre2):]: v for k, v in w.items() if k.startswith(pre2)}
+        stacks, rels = [self.stack], [self._rel]
+        if self.stack2 is not None:
+            pre2 = self.name + "_posterior_conv2_"
+            self._rel2 = {k[len(pre2):]: v for k, v in w.items() if k.startswith(pre2)}
+            stacks.append(self.stack2)
+            rels.append(self._rel2)
+        if self.prior_stack is not None:
+            prep = self.name + "_prior_conv1_"
+            self._rel_p = {k[len(prep):]: v for k, v in w.items() if k.startswith(prep)}
+            stacks.append(self.prior_stack)
+            rels.append(self._rel_p)
         if self._prep is None:
-            self._prep = PrepBatch([self.stack, self.stack2])
-        self._prep.run([self._rel, self._rel2])
+            self._prep = PrepBatch(stacks)
+        self._prep.run(rels)
 
     def up(self, h, eps=None):
         """h: output of up_conv1 [B, 2 n_h + 2 n_z, H, W].  Returns the input of up_conv2 (before its nonlinearity):
         h_det for 'down_iaf2_nl' (models.py:180-182), concat([h_det, z]) for 'up_iaf2_nl' (:168-176; needs eps)."""
         n_h, n_z = self.n_h, self.n_z
-        if self.posterior == "down_iaf2_nl2":
+        if self.posterior == "down_iaf2_nl2" or self.prior == "made":
             # as 'down_iaf2_nl' (models.py:179-181); the chain's kernels read the conv output itself, so what is kept of it are views
             _check_act(h, "h (up_conv1 output)")
             if h.dim() != 4 or h.shape[1] != 2 * n_h + 2 * n_z:
@@ -101,8 +144,10 @@ class CVAELayerIAF(object):
     def down_q(self, h, eps=None):
         """h: output of down_conv1 [B, 2 n_h + 4 n_z, H, W] ('down_iaf2_nl', 'down_iaf2_nl2') or [B, n_h + 2 n_z, H, W] ('up_iaf2_nl').
         Returns dict(h = concat([h_det, z]) for down_conv2, kl [B, n_z, H, W] = logqs - logps (:328), kl_sum [B] (:455),
-        obj_kl (:458-466: scalar tensor when kl_min > 0, else kl_sum))."""
+        obj_kl (:458-466: scalar tensor when kl_min > 0, else kl_sum)).  With prior 'made' h is [B, 3 n_h + 2 n_z, H, W]."""
         n_h, n_z, st = self.n_h, self.n_z, self._st
+        if self.prior == "made":
+            return self._down_q_made(h, eps)
         if self.posterior == "down_iaf2_nl2":
             return self._down_q_chain(h, eps)
         if self.posterior == "down_iaf2_nl":
@@ -199,6 +244,116 @@ class CVAELayerIAF(object):
         grads.update({self.name + "_posterior_conv2_" + k: v for k, v in grads2.items()})
         return dict(d_up_conv1=d_uc1, d_down_conv1=d_dc1, grads=grads)
 
+    def _down_q_made(self, h, eps):
+        """prior 'made' (models.py:272-291, 304-309, 317-318): iaf_made_head, the posterior's one or two steps, the prior's step on
+        (z, made_context), iaf_made_tail, the free bits.  Everything is ordered on the current stream and nothing synchronises with the
+        host, so the call is capturable after a warm-up on the capturing stream.  With channel counts that are multiples of 16 these are
+        the library's launches alone, with no torch arithmetic; embedded stacks (smaller counts) add torch's zero fills and strided
+        copies around every step."""
+        n_h, n_z, st = self.n_h, self.n_z, self._st
+        if st is None or "up_conv1" not in st:
+            raise RuntimeError("down_q() follows up()")
+        if eps is None:
+            raise ValueError("'%s' samples the posterior in the down pass: pass eps" % self.posterior)
+        up = st["up_conv1"]
+        B, H, W = int(up.shape[0]), int(up.shape[2]), int(up.shape[3])
+        _check_act(h, "h (down_conv1 output)", (B, 3 * n_h + 2 * n_z, H, W))
+        _check_act(eps, "eps", (B, n_z, H, W))
+        lib = _capi.lib()
+        z0, logq0 = torch.empty_like(eps), torch.empty_like(eps)
+        context = torch.empty(B, n_h, H, W, dtype=torch.float32, device=h.device)
+        made_context = torch.empty_like(context)
+        _capi.check(lib.iaf_made_head(_ptr(up), _ptr(h), _ptr(eps), _ptr(z0), _ptr(logq0), _ptr(context), _ptr(made_context), B, n_h, n_z,
+                                      H * W, _stream()))
+        step = lambda s: s.iaf_step_train if self.training else s.iaf_step
+        z1, s1 = step(self.stack)(z0, context)                                                            # :281-285
+        z, s2 = step(self.stack2)(z1, context) if self.stack2 is not None else (z1, None)                 # :286-291
+        u, s_p = step(self.prior_stack)(z, made_context)                                                  # :305-308
+        kl = torch.empty_like(eps)
+        h_out = torch.empty(B, n_h + n_z, H, W, dtype=torch.float32, device=h.device)
+        _capi.check(lib.iaf_made_tail(_ptr(h), _ptr(logq0), _ptr(s1), _ptr(s2), _ptr(z), _ptr(u), _ptr(s_p), _ptr(kl), _ptr(h_out), B, n_h,
+                                      n_z, H * W, _stream()))
+        st.pop("gate", None)
+        if self.training and self.kl_min > 0:            # the gate of the free bits is what backward() multiplies with
+            kl_sum, kl_obj, st["gate"] = kl_free_bits(kl, self.kl_min, want_gate=True)
+        else:
+            kl_sum, kl_obj = kl_free_bits(kl, self.kl_min)
+        st.update(down_conv1=h, z0=z0, context_sum=context, made_context=made_context, z1=z1, s1=s1, z=z, s2=s2, u=u, s_p=s_p)
+        obj_kl = kl_obj[0] if self.kl_min > 0 else kl_sum                                                  # :458-466
+        return dict(h=h_out, z=z, kl=kl, kl_sum=kl_sum, obj_kl=obj_kl)
+
+    def _backward_made(self, d_h, d_obj, d_up):
+        """T.grad with prior 'made': kl holds s_p + u^2/2 of the prior's step, so that step's backward runs first with (dz_new, dlogsd) =
+        (G u, G) (iaf_made_backward_pre); its dz joins the z part of d_h (iaf_made_backward_join); then the posterior's steps in reverse
+        order, each with dlogsd = G, and iaf_made_backward_post.  d_obj as in _backward_chain."""
+        n_h, n_z, st = self.n_h, self.n_z, self._st
+        z, up, down = st["z"], st["up_conv1"], st["down_conv1"]
+        B, H, W = int(z.shape[0]), int(z.shape[2]), int(z.shape[3])
+        _check_act(d_h, "d_h", (B, n_h + n_z, H, W))
+        if d_up is not None:
+            _check_act(d_up, "d_up", (B, n_h, H, W))
+        free_bits = self.kl_min > 0
+        if free_bits:
+            if "gate" not in st:
+                raise RuntimeError("backward() with free bits follows down_q() in training mode")
+            gate, dko = st["gate"], None
+            gscale = (1.0 if d_obj is None else float(d_obj)) / B    # obj_kl is ONE scalar per layer (models.py:460-461)
+        else:
+            gate, gscale = None, 0.0
+            dko = torch.ones(B, dtype=torch.float32, device=z.device) if d_obj is None else d_obj
+            _check_act(dko, "d_obj", (B,))
+        lib = _capi.lib()
+        du, G, dz = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
+        d_dc1 = torch.empty_like(down)
+        d_uc1 = torch.empty_like(up)
+        _capi.check(lib.iaf_made_backward_pre(_ptr(st["u"]), _ptr(d_h), _ptr(gate), gscale, _ptr(dko), _ptr(du), _ptr(G), _ptr(d_dc1), B,
+                                              n_h, n_z, H * W, _stream()))
+        dz_p, d_mctx, grads_p = self.prior_stack.iaf_step_backward(z, st["made_context"], st["u"], st["s_p"], du, G, self._rel_p)
+        _capi.check(lib.iaf_made_backward_join(_ptr(d_h), _ptr(dz_p), _ptr(d_mctx), _ptr(dz), _ptr(d_dc1), B, n_h, n_z, H * W, _stream()))
+        ctx = st["context_sum"]
+        grads = {self.name + "_prior_conv1_" + k: v for k, v in grads_p.items()}
+        dctx2 = None
+        if self.stack2 is not None:
+            dz, dctx2, grads2 = self.stack2.iaf_step_backward(st["z1"], ctx, z, st["s2"], dz, G, self._rel2)
+            grads.update({self.name + "_posterior_conv2_" + k: v for k, v in grads2.items()})
+        dz0, dctx1, grads1 = self.stack.iaf_step_backward(st["z0"], ctx, st["z1"], st["s1"], dz, G, self._rel)
+        grads.update({self.name + "_posterior_conv1_" + k: v for k, v in grads1.items()})
+        _capi.check(lib.iaf_made_backward_post(_ptr(up), _ptr(down), _ptr(st["z0"]), _ptr(dz0), _ptr(G), _ptr(dctx1), _ptr(dctx2),
+                                               _ptr(d_up), _ptr(d_uc1), _ptr(d_dc1), B, n_h, n_z, H * W, _stream()))
+        return dict(d_up_conv1=d_uc1, d_down_conv1=d_dc1, grads=grads)
+
+    def down_p(self, h, eps, exact=True, max_sweeps=64, tol=1e-6, check_every=4, stats=None):
+        """models.py:330-359 between the plain convs: h is the output of down_conv1 (in this layer's layout), eps [B, n_z, H, W] the
+        noise; returns concat([h_det, z]) for down_conv2.  prior 'diag': z = pz_mean + eps exp(pz_logsd) (:334-337).  prior 'made':
+        exact=False is the reference, z = eps (:338-340, 'TODO: SAMPLES FROM MADE PRIOR'); exact=True is the ancestral sample
+        z_i ~ N(0.1 m_i(z_<i), exp(2 * 0.1 s_i(z_<i))), the solution of z = 0.1 m(z) + exp(0.1 s(z)) eps, by the prior stack's queued
+        inverse step (Jacobi sweeps; max_sweeps, tol, check_every and stats as ARStack.iaf_step_inverse_queued: exact after H W n_z
+        sweeps for any weights).  Ordered on the current stream with no host synchronisation: capturable after a warm-up.  Beside the
+        library's launches, exact=True makes one torch copy (the contiguous made_context), and an embedded prior stack pads and slices
+        with torch."""
+        n_h, n_z = self.n_h, self.n_z
+        _check_act(h, "h (down_conv1 output)")
+        if self.prior == "made":
+            n_down = 3 * n_h + 2 * n_z
+        else:
+            n_down = n_h + 2 * n_z if self.posterior == "up_iaf2_nl" else 2 * n_h + 4 * n_z
+        if h.dim() != 4 or h.shape[1] != n_down:
+            raise ValueError("h must be [B, %d, H, W], got %s" % (n_down, tuple(h.shape)))
+        B, H, W = int(h.shape[0]), int(h.shape[2]), int(h.shape[3])
+        _check_act(eps, "eps", (B, n_z, H, W))
+        lib = _capi.lib()
+        h_out = torch.empty(B, n_h + n_z, H, W, dtype=torch.float32, device=h.device)
+        if self.prior == "diag":
+            _capi.check(lib.iaf_diag_prior_sample(_ptr(h), _ptr(eps), _ptr(h_out), B, n_down, n_h, n_z, H * W, _stream()))
+            return h_out
+        z = eps
+        if exact:
+            made_context = h.narrow(1, n_h, n_h).contiguous()
+            z, _ = self.prior_stack.iaf_step_inverse_queued(eps, made_context, max_sweeps=max_sweeps, tol=tol, check_every=check_every,
+                                                            stats=stats)
+        _capi.check(lib.iaf_made_tail(_ptr(h), None, None, None, _ptr(z), None, None, None, _ptr(h_out), B, n_h, n_z, H * W, _stream()))
+        return h_out
+
     def backward(self, d_h, d_obj=None, d_up=None):
         """T.grad (graphy/misc/optim.py:102) of  <d_up, up()> + <d_h, down_q()['h']> + <d_obj, obj_kl>  through the lines
         models.py:139-146,168-176,272-298,454-466.  Must follow up() and down_q() in training mode on the same inputs.
@@ -207,6 +362,8 @@ class CVAELayerIAF(object):
         -- gradients of the two conv outputs in the reference's channel order -- and grads keyed like the reference's w)."""
         if not self.training or self._st is None or "z" not in self._st:
             raise RuntimeError("backward() follows up() and down_q() in training mode")
+        if self.prior == "made":
+            return self._backward_made(d_h, d_obj, d_up)
         if self.posterior == "down_iaf2_nl2":
             return self._backward_chain(d_h, d_obj, d_up)
         n_h, n_z, st = self.n_h, self.n_z, self._st

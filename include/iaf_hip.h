@@ -365,6 +365,39 @@ int iaf_chain_backward_pre(const float* down_conv1_out, const float* z2, const f
 int iaf_chain_backward_post(const float* up_conv1_out, const float* down_conv1_out, const float* z0, const float* dz0, const float* G,
                             const float* dctx1, const float* dctx2, const float* d_up, float* d_up_conv1, float* d_down_conv1,
                             int B, int n_h, int n_z, int HW, void* stream);
+/* The elementwise path of the Theano layer's 'made' prior (models.py:36-38, 304-309) with the posteriors 'down_iaf2_nl' and
+ * 'down_iaf2_nl2': around the posterior's one or two steps and the PRIOR's step (a third stack, <name>_prior_conv1, plain ordering,
+ * on made_context), all of them iaf_step_forward[_train] / iaf_step_backward calls.  Layouts:
+ *   up_conv1_out   [B, 2 n_h + 2 n_z, HW] = [h_det | qz_mean | qz_logsd | up_context]                 (as for every posterior)
+ *   down_conv1_out [B, 3 n_h + 2 n_z, HW] = [h_det | made_context | rz_mean | rz_logsd | down_context]
+ * d_up_conv1 / d_down_conv1 have the same layouts.  With (u, s_p) = the prior stack's step on (z, made_context), that is
+ * u = (z - 0.1 m) / exp(0.1 s), s_p = 0.1 s, the prior's density is logps = -(log 2pi) / 2 - s_p - u^2 / 2.
+ *   head: z0, logq0, context as iaf_chain_head;  made_context [B, n_h, HW] = the contiguous copy of that channel group
+ *   tail: kl_elem = ((logq0 + logdet1) [+ logdet2]) + ((log 2pi) / 2 + s_p + u^2 / 2) [B, n_z, HW] (logdet2 NULL: one flow),
+ *         h_out [B, n_h + n_z, HW] = [h_det | z].  kl_elem NULL: only h_out is written, and logq0, logdet1, u, s_p may be NULL
+ *   pre:  G = gate[c] * gscale (free bits) or dko[b] (gate = NULL), expanded to [B, n_z, HW];  du = G u;  channels [0, n_h) of
+ *         d_down_conv1 = d_h[h_det part], its other channels are not touched.  (du, G) are the (dz_new, dlogsd) of the prior step's
+ *         iaf_step_backward, which returns dz_p and d_made_context
+ *   join: dz = d_h[z part] + dz_p [B, n_z, HW] (dz_new of the last posterior step's backward);  channels [n_h, 2 n_h) of
+ *         d_down_conv1 = d_made_context, its other channels are not touched
+ *   post: dmean = dz0, dlogsd = dz0 (z0 - mean) - G, dcontext = dctx1 [+ dctx2] (dctx2 NULL: one flow);  d_up_conv1 = [d_up or 0 |
+ *         dmean | dlogsd | dcontext];  channels [2 n_h, 3 n_h + 2 n_z) of d_down_conv1 = [dmean | dlogsd | dcontext]
+ * iaf_diag_prior_sample is down_p (models.py:334-337) of the DIAG prior: down_conv1_out [B, n_down, HW] = [h_det | pz_mean | pz_logsd
+ * | ...] with n_down >= n_h + 2 n_z channels (either diag layout);  h_out = [h_det | pz_mean + eps exp(pz_logsd)].
+ * Sizes, alignment and argument checks as for the chain's entry points. */
+int iaf_made_head(const float* up_conv1_out, const float* down_conv1_out, const float* eps, float* z0, float* logq0, float* context,
+                  float* made_context, int B, int n_h, int n_z, int HW, void* stream);
+int iaf_made_tail(const float* down_conv1_out, const float* logq0, const float* logdet1, const float* logdet2, const float* z,
+                  const float* u, const float* s_p, float* kl_elem, float* h_out, int B, int n_h, int n_z, int HW, void* stream);
+int iaf_made_backward_pre(const float* u, const float* d_h, const float* gate, float gscale, const float* dko, float* du, float* G,
+                          float* d_down_conv1, int B, int n_h, int n_z, int HW, void* stream);
+int iaf_made_backward_join(const float* d_h, const float* dz_p, const float* d_made_context, float* dz, float* d_down_conv1,
+                           int B, int n_h, int n_z, int HW, void* stream);
+int iaf_made_backward_post(const float* up_conv1_out, const float* down_conv1_out, const float* z0, const float* dz0, const float* G,
+                           const float* dctx1, const float* dctx2, const float* d_up, float* d_up_conv1, float* d_down_conv1,
+                           int B, int n_h, int n_z, int HW, void* stream);
+int iaf_diag_prior_sample(const float* down_conv1_out, const float* eps, float* h_out, int B, int n_down, int n_h, int n_z, int HW,
+                          void* stream);
 int iaf_kl_combine(const float* logq0, const float* logdet, const float* logp, float* kl, size_t n, void* stream);
 /* out[j] = sum_i mat[i*n + j], i < m: the running `kl_cost += cur_cost` over a model's layers (tf_train.py:198-200) when
  * every layer wrote its [n] KL costs into one row of a [m, n] matrix */
