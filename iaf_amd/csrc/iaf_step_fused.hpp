@@ -14,9 +14,11 @@
 // XCH = 1 (16-pixel rows): the halo rows are EXCHANGED instead -- every hidden layer computes the R rows its workgroup owns, its
 // region holds one row more, and that row is the first row of the block below, handed over through a per-stack, per-stream buffer
 // in device memory.  Round 4's form (round 3's: docs/LAB_NOTEBOOK_r01-r03.md 4.9 item 7):
-//   order      a workgroup takes a TICKET and only waits for lower tickets -- nothing rests on dispatch order or placement (xch_take_*);
+//   order      a workgroup takes a TICKET and only waits for lower tickets -- nothing rests on dispatch order or placement (xch_take_*:
+//              the first helper thread asks, so that no compute wave sits out the ticket's round trip in front of its first loads);
 //   hand-over  the data is the flag: rows are all-ones between launches, copied LDS -> memory -> LDS in 16-byte coalesced sc1
-//              accesses, re-armed by their consumer (xch_export / xch_import);
+//              accesses, re-armed by their consumer BEHIND the barrier that hands the row to the compute waves
+//              (xch_export / xch_import, xch_handover, xch_rearm);
 //   who        four HELPER waves per workgroup (HLP), one beside each compute wave, do all of it in vector-memory queues of their
 //              own while the compute waves multiply the taps of their own rows (StepPart) -- the helper section;
 //   failure    bounded waits; a wait that gives up imports NaN and raises a sticky device word and a host-visible one.
@@ -538,15 +540,21 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
     constexpr unsigned XNLST = IAF_XCTL_LISTS;
     unsigned xcc = 0, xdead = 0;
     unsigned long long xdone = 0, xlists_done = 0;
-    [[maybe_unused]] unsigned xmine = 0, xmine_n = 0;                    // (thread 0: the list its ticket came from, that list's items)
+    [[maybe_unused]] unsigned xmine = 0, xmine_n = 0;                    // (the ticket's thread: the list its ticket came from, that list's items)
     int xslot = 0;
     int half = 0;                                                        // PAIR: which channel half this workgroup computes
     [[maybe_unused]] unsigned long long xt0 = 0;
     [[maybe_unused]] unsigned xlist = 0, xnl = 1;
     unsigned* xmail = (unsigned*)(smem + (size_t)G::CTX_OFF * 16);          // (the context staging area: not written before the first conv is done)
+    // WHO takes it: the first HELPER thread.  An atomic with return is read back on the spot (the compiler's wave-level form of it ends in a
+    // v_readfirstlane of the result), so the wave that asks sits out the whole round trip -- a compute wave would issue its first-conv weight
+    // requests and its zero fill only behind it, and the workgroup would meet it at the barrier of xch_take_finish.  The helpers have nothing
+    // to do until the item is known.  The counters that follow the ticket (xdone, xlists_done: xch_next_epoch_*) stay with that thread.
+    constexpr int XTID = 64 * NW_COMPUTE;
+    static_assert(!TKT || HELP, "the ticket is a helper thread's");
     auto xch_take_begin = [&]() {
         if constexpr (TKT) {
-            if (tid == 0) {
+            if (tid == XTID) {
                 asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
                 xcc &= 7u;
                 xlist = xcc & (XNLST - 1u);                                               // one list per XCD
@@ -562,7 +570,7 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
     };
     auto xch_take_finish = [&]() {
         if constexpr (TKT) {
-            if (tid == 0) {
+            if (tid == XTID) {
                 unsigned long long v = xt0;
                 unsigned y = xlist, t = 0, ny = 0;
                 bool found = false;
@@ -591,23 +599,24 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
             r0 = rbk * R;
             img_z = (size_t)b * NZ * HW; img_h = (size_t)b * NH * HW;
             xslot = b * p.nrb + rbk;
-            if (xdead && tid == 0) {
+            if (xdead && tid == XTID) {
                 if (p.xerr) __hip_atomic_store(p.xerr, 0x100u | xdead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(p.xctl + IAF_XCTL_STICKY, (unsigned long long)xdead, __ATOMIC_RELAXED, XSCOPE);
             }
         }
     };
     // ... and, once all of this launch's tickets are taken, the counters of the next launch: two steps, so that no wave ever waits
-    // for a counter (each result is looked at a phase after its request)
+    // for a counter (each result is looked at a phase after its request, where the ticket's wave has waited for younger loads anyway: a -- the
+    // context rows are staged; b -- the first imported row, or the partner's half, is taken)
     auto xch_next_epoch_a = [&]() {
         if constexpr (TKT) {
-            if (tid == 0 && xmine_n && (unsigned)xdone == xmine_n - 1u)
+            if (tid == XTID && xmine_n && (unsigned)xdone == xmine_n - 1u)
                 xlists_done = __hip_atomic_fetch_add(p.xctl + IAF_XCTL_DONE, 1ull, __ATOMIC_RELAXED, XSCOPE) + 1ull;
         }
     };
     auto xch_next_epoch_b = [&]() {
         if constexpr (TKT) {
-            if (tid == 0 && (unsigned)xlists_done == (unsigned)(p.B < (int)XNLST ? p.B : (int)XNLST)) {
+            if (tid == XTID && (unsigned)xlists_done == (unsigned)(p.B < (int)XNLST ? p.B : (int)XNLST)) {
                 for (int y = 0; y < (int)XNLST; ++y) {
                     __hip_atomic_store(p.xctl + 32 * y, 0ull, __ATOMIC_RELAXED, XSCOPE);
                     __hip_atomic_store(p.xctl + 32 * y + 16, 0ull, __ATOMIC_RELAXED, XSCOPE);
@@ -1009,8 +1018,14 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
             }
         }
     };
-    // row R of the region <- row 0 of the block below (zeros past the image); the compute waves meet it at their next barrier
-    auto xch_import = [&](int l, int reg) {
+    // row R of the region <- row 0 of the block below (zeros past the image); the compute waves meet it at their next barrier.
+    // Three steps, in this order: xch_import takes the row and writes it to LDS; xch_handover is the barrier the compute waves wait at;
+    // xch_rearm puts XSENT back -- BEHIND the barrier and behind whatever the helper owes the compute waves in that phase.  The re-arming
+    // stores are sc1 and take ~1.5 k cycles to be acknowledged; vmcnt counts in order, so issued in front of the LDS stores (as they were
+    // until this order) the wait that guards the row's registers, s_waitcnt vmcnt(2), waited for the first of them: 1.5 k cycles of the
+    // compute waves' wait per import.  Every row that xch_import reports as taken is re-armed by its caller before the kernel ends.
+    auto xch_import = [&](int l, int reg) -> bool {
+        bool taken = false;
         if constexpr (XCH) {
             f32x4* dst = smem4 + reg + (R * RS + 1) * H16;
             if (r0 + R < H) {
@@ -1026,13 +1041,16 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                 int it = xdead ? tmo : 0;
                 if (p.dbg && htid == 0) p.dbg[(size_t)blockIdx.x * 32 + (l == 0 ? 14 : 18)] = __builtin_readcyclecounter();
                 while (it < tmo) {
-                    bool ok = true;
+                    unsigned ok = 1u;
 #pragma unroll
                     for (int u = 0; u < XNLH; ++u) t[u] = __builtin_amdgcn_raw_buffer_load_b128(r, 16 * (htid + 256 * u), 0, XSC1);
+                    // (no short-circuit: with && and || the padding lanes branch around the wait for their load, the compiler then carries
+                    //  "a row load may still be outstanding" out of the loop, and the first write to one of its registers behind younger
+                    //  STORES -- the export, the re-arming -- waits for those stores' acknowledgement)
 #pragma unroll
                     for (int u = 0; u < XNLH; ++u)
-                        ok = ok && (((pad >> u) & 1u) || (t[u][0] != XSENT && t[u][1] != XSENT && t[u][2] != XSENT && t[u][3] != XSENT));
-                    if (__all(ok)) break;
+                        ok &= ((pad >> u) & 1u) | (unsigned)((t[u][0] != XSENT) & (t[u][1] != XSENT) & (t[u][2] != XSENT) & (t[u][3] != XSENT));
+                    if (__all(ok != 0u)) break;
                     __builtin_amdgcn_s_sleep(8);                                     // (the row is not there yet: it is the only thing this wave waits for)
                     ++it;
                 }
@@ -1041,11 +1059,8 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                     p.dbg[(size_t)blockIdx.x * 32 + (l == 0 ? 24 : 25)] = (unsigned long long)it + 1;
                     p.dbg[(size_t)blockIdx.x * 32 + 26] = (unsigned long long)xslot + 1;
                 }
-                if (it < tmo) {                                                      // taken: the buffer is all XSENT again for the next launch
-#pragma unroll
-                    for (int u = 0; u < XNLH; ++u)
-                        __builtin_amdgcn_raw_buffer_store_b128(u32x4{XSENT, XSENT, XSENT, XSENT}, r, 16 * (htid + 256 * u), 0, XSC1);
-                } else {                                                             // gave up (or the buffer is marked dead): NaN, loudly
+                taken = it < tmo;                                                    // (wave-uniform: every lane leaves the loop at the same sweep)
+                if (!taken) {                                                        // gave up (or the buffer is marked dead): NaN, loudly
 #pragma unroll
                     for (int u = 0; u < XNLH; ++u) t[u] = u32x4{XNAN, XNAN, XNAN, XNAN};
                     if (lane == 0 && !xdead) {
@@ -1058,6 +1073,23 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                 if (p.dbg && htid == 0) p.dbg[(size_t)blockIdx.x * 32 + (l == 0 ? 17 : 20)] = __builtin_readcyclecounter();
             } else {
                 for (int i = htid; i < XNU; i += 256) dst[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        return taken;
+    };
+    // the hand-over: the barrier as soon as the LDS stores are done (s_barrier counts waves: it pairs with the compute waves' __syncthreads)
+    auto xch_handover = [&]() {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    };
+    // taken: the buffer is all XSENT again for the next launch
+    auto xch_rearm = [&](int l, bool taken) {
+        if constexpr (XCH) {
+            if (taken) {
+                const __amdgpu_buffer_rsrc_t r = xch_rsrc(l, xslot + 1);
+#pragma unroll
+                for (int u = 0; u < XNLH; ++u)
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{XSENT, XSENT, XSENT, XSENT}, r, 16 * (htid + 256 * u), 0, XSC1);
             }
         }
     };
@@ -1211,6 +1243,7 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                         *(f32x4*)(creg + c * CSTR + g4) = FLIP ? f32x4{t[3], t[2], t[1], t[0]} : t;
                     }
                 }
+                xch_next_epoch_a();
                 __syncthreads();                                  // first conv done, context staged
                 if constexpr (HL0) {
                     if (q0 >= 0) {
@@ -1235,10 +1268,13 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
             static_for<DEPTH - 1>([&](auto lm_c) {
                 constexpr int l = decltype(lm_c)::value + 1;
                 constexpr int IN_REG = ((l - 1) & 1) ? G::HREG1 : G::HREG0, OUT_REG = (l & 1) ? G::HREG1 : G::HREG0;
+                [[maybe_unused]] bool xtaken = false;
                 if constexpr (XCH) {
-                    xch_import(l - 1, IN_REG);
-                    __syncthreads();                              // row R of h_{l-1} is there
+                    xtaken = xch_import(l - 1, IN_REG);
+                    xch_handover();                               // row R of h_{l-1} is there
                 }
+                // (the ticket's thread has just waited for the row's loads, which are younger than its count of the finished lists)
+                if constexpr (l == 1) xch_next_epoch_b();
                 if constexpr (HLEFT) {
                     // this helper's left-over unit of layer l: the tile its compute wave would have held in its last slot, the pixel tile of
                     // that wave's group -- all of the layer's taps (the row below is in LDS), bias + ELU + split -> the layer's region
@@ -1280,10 +1316,15 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                 }
                 __syncthreads();                                  // layer l's epilogue done
                 xch_export(l, OUT_REG);
+                // (the re-arming behind the helper's own unit -- its K loop waits for loads, and a wait for a load also waits for every older
+                //  store of the wave's queue -- and behind the export, which the block above is waiting for; what follows in the queue are the
+                //  loads of the next import, which the export's stores precede anyway)
+                xch_rearm(l - 1, xtaken);
             });
+            if constexpr (DEPTH == 1) xch_next_epoch_b();
             if constexpr (XCH) {
                 constexpr int LAST_REG = ((DEPTH - 1) & 1) ? G::HREG1 : G::HREG0;
-                xch_import(DEPTH - 1, LAST_REG);
+                const bool xtaken = xch_import(DEPTH - 1, LAST_REG);
                 if constexpr (G::HOUT) {
                     // the output pair's taps of the row below, odd steps: this helper's compute wave's tiles, both pixel tiles
                     constexpr int NPTO_ = (R * W + 15) / 16;
@@ -1299,7 +1340,7 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                         ring_load(std::integral_constant<int, 0>{}, std::integral_constant<int, NTWO * NPL>{}, wroh[decltype(i)::value], wboh, 2 * NZT,
                                   ot, PartOBH{}, decltype(i)::value, std::integral_constant<int, -1>{}, 0);
                     });
-                    __syncthreads();                              // row R of the last hidden layer is there
+                    xch_handover();                               // row R of the last hidden layer is there
                     conv_phase(std::integral_constant<int, RDOH>{}, std::integral_constant<int, NPTO_>{}, std::integral_constant<int, NTWO>{},
                                std::integral_constant<int, R>{}, std::integral_constant<int, (1 << NPTO_) - 1>{}, LAST_REG,
                                H16, H8, wboh, 2 * NZT, ot, wroh, accoh, PartOBH{}, std::integral_constant<int, 0>{},
@@ -1315,8 +1356,9 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                             for (int r = 0; r < 4; ++r) part1[pix * G::XB_STRIDE + ot[j] * 16 + 4 * kk + r] = accoh[q][j][r];
                         }
                 } else {
-                    __syncthreads();                              // row R of the last hidden layer is there
+                    xch_handover();                               // row R of the last hidden layer is there
                 }
+                xch_rearm(DEPTH - 1, xtaken);                     // (behind the helper's part of the output pair: see above)
             }
             if constexpr (PAIR) {
                 if (!((p.xknob & 8u) && b == 0 && rbk == 0 && half == 1)) pair_export();     // (test knob 8: one half is never handed over)
@@ -1509,7 +1551,6 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
                        std::integral_constant<int, G::rows_h(0)>{}, std::integral_constant<int, EM0>{}, G::ZREG, Z16, Z8, wb0, NHT, htile,
                        wr0, acc0, PartL0{}, g_c, SET, 0);
         IAF_FSTAMP(6);
-        xch_next_epoch_a();
         if constexpr (!HELP) store_ctx();
         if constexpr (DEPTH == 1) load_final_operands();
         preload_after(std::integral_constant<int, 0>{});
@@ -1644,7 +1685,6 @@ __attribute__((amdgpu_waves_per_eu(HLP ? 2 : 1, HLP ? 2 : 1))) void iaf_step_fus
     // ---- output pair: packed tiles (m_0, s_0, m_1, s_1, ...), partial sums -> exchange buffer [K part][pixel][2 n_z] -------
     // (the operands of the final transform are fetched first: they travel while the output pair is multiplied)
     float* xbuf = (float*)(smem + (size_t)G::XB_OFF * 16);
-    xch_next_epoch_b();
     if constexpr (PAIR) {
         f32x4 acco[NPTO][NTWO];
         constexpr int LAST_REG = ((DEPTH - 1) & 1) ? G::HREG1 : G::HREG0;

@@ -61,7 +61,7 @@ if (t[:, 28] != 0).any():
         md = lambda a, b_: np.median(k[:, a] - k[:, b_])
         print("    compute waves (wave 0): second conv own taps %.0f | wait for the helpers' row %.0f | taps below %.0f;  output pair own taps %.0f | wait %.0f | taps below %.0f" % (
             md(28, 2), md(15, 28), md(7, 15), md(29, 3), md(21, 29), md(4, 21)))
-        print("    helpers (first helper wave): import 1 asks %+.0f after the first epilogue's barrier, row complete +%.0f later, re-arm + LDS stores +%.0f;  import 2: asks %+.0f after the second epilogue's barrier, complete +%.0f, stores +%.0f" % (
+        print("    helpers (first helper wave): import 1 asks %+.0f after the first epilogue's barrier, row complete +%.0f later, LDS stores (before profiles/exchange_waits: re-arm + LDS stores) +%.0f;  import 2: asks %+.0f after the second epilogue's barrier, complete +%.0f, stores +%.0f" % (
             md(14, 2), md(16, 14), md(17, 16), md(18, 3), md(19, 18), md(20, 19)))
 if (t[:, 28] == 0).all() and (t[:, 29] != 0).any() and (t[:, 19] != 0).any():
     # the pair form (8-pixel rows): two workgroups per (image, two rows); dbg[26] = 2 * item + half + 1
