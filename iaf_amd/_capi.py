@@ -56,6 +56,7 @@ SIGNATURES = {
     "iaf_error_string": (ctypes.c_char_p, [ctypes.c_int]),
     "iaf_device_count": (ctypes.c_int, []),
     "iaf_stack_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "iaf_stack_create_resnet": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "iaf_stack_destroy": (ctypes.c_int, [_vp]),
     "iaf_stack_prepare": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "iaf_prep_batch_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int]),
@@ -113,6 +114,7 @@ SIGNATURES = {
     "iaf_stack_set_tuning": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5),
     "iaf_stack_set_precision": (ctypes.c_int, [_vp, ctypes.c_int]),
     "iaf_stack_get_precision": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4),
+    "iaf_stack_get_dgrad_precision": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4),
     "iaf_stack_set_tuning_bf3": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6),
     "iaf_stack_set_fuse_first": (ctypes.c_int, [_vp, ctypes.c_int]),
     "iaf_stack_set_fuse_step": (ctypes.c_int, [_vp, ctypes.c_int]),

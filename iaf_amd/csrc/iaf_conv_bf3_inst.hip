@@ -25,6 +25,13 @@ static conv_fn_t pick_mode_bf3(int inmode, int epi) {
     }
     if (epi == EPI_DGRAD)     // data gradient of a masked conv: dY pixel-major, transposed bf16x3 pack, mirrored taps
         return inmode == IN_PIXMAJOR ? iaf_conv_bf3_kernel<NT, IAF_PPW, IAF_PXT, IAF_KS, IN_PIXMAJOR, EPI_DGRAD, IAF_WCO> : nullptr;
+    if (epi == EPI_RES) {     // residual stream of the masked ResNet (iaf_stack_create_resnet)
+        if (inmode == IN_PIXMAJOR) return iaf_conv_bf3_kernel<NT, IAF_PPW, IAF_PXT, IAF_KS, IN_PIXMAJOR, EPI_RES, IAF_WCO>;
+        if (inmode == IN_NCHW) return iaf_conv_bf3_kernel<NT, IAF_PPW, IAF_PXT, IAF_KS, IN_NCHW, EPI_RES, IAF_WCO>;
+        return nullptr;
+    }
+    if (epi == EPI_DGRAD_RES)
+        return inmode == IN_PIXMAJOR ? iaf_conv_bf3_kernel<NT, IAF_PPW, IAF_PXT, IAF_KS, IN_PIXMAJOR, EPI_DGRAD_RES, IAF_WCO> : nullptr;
     if (epi == EPI_OUT) {     // the output pair always reads the last hidden layer (depth_ar = 0 stays on the fp32 kernel)
         if constexpr (NT % 2 == 0) {
             if (inmode == IN_PIXMAJOR) return iaf_conv_bf3_kernel<NT, IAF_PPW, IAF_PXT, IAF_KS, IN_PIXMAJOR, EPI_OUT, IAF_WCO>;

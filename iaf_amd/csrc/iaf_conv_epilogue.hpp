@@ -96,6 +96,24 @@ __device__ __forceinline__ void epi_load(const ConvP& p, const EpiGeom& g, int c
 #pragma unroll
             for (int r = 0; r < 4; ++r) { o.pre0[r] = p.qm[cb + (size_t)r * HW]; o.pre1[r] = p.ql[cb + (size_t)r * HW]; }
         }
+    } else if (EPI == EPI_RES) {    // residual stream of the masked ResNet (ar.py:428-448, 502-504): EPI_HIDDEN's operands + the skip (in b1: one-tile units)
+        o.b0 = *(const f32x4*)(p.bias + cot * 16 + 4 * g.kk);
+        if (p.ctx) {
+            const size_t cb = ((size_t)g.bimg * p.cout + cot * 16 + 4 * g.kk) * HW + g.pp;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o.pre0[r] = p.ctx[cb + (size_t)r * HW];
+            if (p.ctx2) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o.pre1[r] = p.ctx2[cb + (size_t)r * HW];
+            }
+        }
+        if (p.skip) o.b1 = *(const f32x4*)(p.skip + (size_t)g.Pl * p.cout + cot * 16 + 4 * g.kk);      // raw stream, pixel-major
+    } else if (EPI == EPI_DGRAD_RES) {  // data gradient on the residual stream: saved elu(h_i) and the stream's gradient, both pixel-major
+        if (p.mode == MODE_DGRAD_SKIP) {
+            const int co = cot * 16 + 4 * g.kk;
+            o.pre0 = *(const f32x4*)(p.zin + (size_t)g.Pl * p.cout + co);
+            o.pre1 = *(const f32x4*)(p.skip + (size_t)g.Pl * p.cout + co);
+        }
     } else if (EPI == EPI_PRIOR) {  // cot = the unit's first launched tile: biases of both pack tiles; a z unit's noise
         const int u = cot >> 1;
         o.b0 = *(const f32x4*)(p.bias + prior_pack_tile(p, cot) * 16 + 4 * g.kk);
@@ -185,6 +203,39 @@ __device__ __forceinline__ void epi_apply(const ConvP& p, const EpiGeom& g, int 
             const size_t cb = ((size_t)g.bimg * p.cout + co) * HW + g.pp;
 #pragma unroll
             for (int r = 0; r < 4; ++r) p.out0[cb + (size_t)r * HW] = v[r] + o.pre0[r] * __expf(-o.pre1[r]);
+        }
+    } else if (EPI == EPI_RES) {        // h = conv(.) + bias [+ border] [+ ctx (+ ctx2)];  skip: h = skip + 0.1 h (ar.py:441);  raw -> y, elu(h) -> y2
+        const int co = cot * 16 + 4 * g.kk;
+        f32x4 v = v0 + o.b0;
+        if (p.border) {
+#pragma unroll
+            for (int t = 1; t < NTP; ++t)
+                if (g.outside & (1u << t)) v += *(const f32x4*)(p.border + (size_t)(t - 1) * p.cout + co);
+        }
+        if (p.ctx) {
+            if (p.ctx2) v += (o.pre0 + o.pre1);
+            else v += o.pre0;
+        }
+        if (p.skip) v = o.b1 + 0.1f * v;
+        *(f32x4*)(p.y + (size_t)g.Pl * p.cout + co) = v;
+        if (p.y2) {                                                // what the next block's conv1 reads (omitted behind the last block)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = elu_f(v[r]);
+            *(f32x4*)(p.y2 + (size_t)g.Pl * p.cout + co) = v;
+        }
+    } else if (EPI == EPI_DGRAD_RES) {  // MODE_DGRAD_RAW: d h_D = W_out^T dY;  MODE_DGRAD_SKIP: d h_i = d h_{i+1} + elu'(h_i) (W_conv1^T d t_i)
+        const int co = cot * 16 + 4 * g.kk;
+        f32x4 v = v0;
+        if (p.mode == MODE_DGRAD_SKIP) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = o.pre1[r] + v[r] * (o.pre0[r] > 0.f ? 1.f : o.pre0[r] + 1.f);
+        }
+        *(f32x4*)(p.y + (size_t)g.Pl * p.cout + co) = v;           // (may be p.skip itself: every element is read and written by one lane)
+        if (p.y2) *(f32x4*)(p.y2 + (size_t)g.Pl * p.cout + co) = 0.1f * v;      // dY of the block's conv2 (h_{i} = h_{i-1} + 0.1 conv2(.))
+        if (p.out0) {                                              // (+ NCHW copy = d context: block 0)
+            const size_t cb = ((size_t)g.bimg * p.cout + co) * HW + g.pp;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p.out0[cb + (size_t)r * HW] = v[r];
         }
     } else if (EPI == EPI_PRIOR) {
         const int u = cot >> 1;

@@ -34,6 +34,11 @@ __device__ __forceinline__ void static_for(F&& f) {
 #define EPI_PRIOR 7    // down_conv1 in prior form (mode "sample", tf_train.py:52-54,56,60-61): only the pz_mean / pz_logsd / h_det tiles;
                        // z = pz_mean + exp(pz_logsd) eps and h_det + bias -> NCHW (iaf_conv_bf3.hpp, iaf_conv_epilogue.hpp)
 
+#define EPI_RES 8      // residual stream of the masked ResNet (graphy/nodes/ar.py:428-448, 478-528): v = acc + bias [+ ctx (+ ctx2)];
+                       // skip != NULL: v = skip + 0.1 v;  y = v (raw, pixel-major);  y2 != NULL: y2 = elu(v) (pixel-major)
+#define EPI_DGRAD_RES 9   // data gradient on the residual stream (its own compile-time epilogue: EPI_DGRAD's code stays what it was):
+                       // modes MODE_DGRAD_RAW / MODE_DGRAD_SKIP
+
 #define MODE_RAW 0        // out0 = m_raw, out1 = s_raw                         (layers.py:166)
 #define MODE_IAF 1        // out0 = (z-0.1m)/exp(0.1s), out1 = 0.1s             (tf_train.py:70-72)
 #define MODE_POSTERIOR 2  // MODE_IAF on z0 rebuilt from the posterior inputs, plus kl elements
@@ -45,6 +50,10 @@ __device__ __forceinline__ void static_for(F&& f) {
 #define MODE_DGRAD_ELU 3  // y = acc * elu'(a) with elu'(a) = (h > 0 ? 1 : h + 1), h = saved activation (p.zin, pixel-major);
                           // optional NCHW copy to p.out0 (d context, layers.py:163-164)
 #define MODE_DGRAD_Z 4    // out0[NCHW] = acc + dz_new * exp(-logsd)   (p.qm = dz_new, p.ql = logsd; tf_train.py:71)
+
+// ... of EPI_DGRAD_RES: y = v (pixel-major; may alias skip), y2 != NULL: y2 = 0.1 v (the dY of the block's second conv), out0 != NULL: NCHW copy
+#define MODE_DGRAD_RAW 7  // v = acc                                   (d h_D = W_out^T dY: the output pair reads the raw stream)
+#define MODE_DGRAD_SKIP 8 // v = skip + acc * elu'(a), elu'(a) from the saved elu(h_i) (p.zin, pixel-major); skip = d h_{i+1} (p.skip, pixel-major)
 
 #define IN_PIXMAJOR 0     // x is [P][c_in] scratch written by a previous EPI_HIDDEN
 #define IN_NCHW 1         // x is an NCHW tensor (z)
@@ -106,6 +115,9 @@ struct ConvP {
     // EPI_PRIOR: 16-channel tiles of n_z (pr_nzt) and of n_h (pr_nht); launched tiles pr_nlt = 2 pr_nzt + 2 ceil(pr_nht / 2), in two-tile units
     // (pz_mean tile u, pz_logsd tile u) for u < pr_nzt, then (h_det tile 2j, 2j+1).  eps / out0 = z [B,n_z,H,W], out1 = h_det [B,n_h,H,W]
     int pr_nzt, pr_nht, pr_nlt;
+    // EPI_RES / EPI_DGRAD_RES (last, so that every older field keeps its offset): the residual stream read (pixel-major [P][cout]) and
+    // the second pixel-major output
+    const float* skip; float* y2;
 };
 
 // Pin the order "MFMAs with memory instructions spread evenly between them" inside the current scheduling region:
@@ -375,6 +387,7 @@ __global__ __launch_bounds__(64 * PXT * WCO * KS) void iaf_conv_kernel(ConvP p) 
     constexpr int NUNIT = ONE_TILE_UNITS ? NT : NT / 2;
     constexpr int NMY = (NUNIT + KS - 1) / KS;
     f32x4 pre0[NMY], pre1[NMY], pbias[NMY * (ONE_TILE_UNITS ? 1 : 2)];
+    f32x4 pre2[EPI == EPI_RES ? NMY : 1];      // EPI_RES: the skip
     auto prefetch_epilogue = [&]() {     // operands that do not depend on the GEMM: bias, context, z
         if (!pvalid) return;
 #pragma unroll
@@ -406,7 +419,13 @@ __global__ __launch_bounds__(64 * PXT * WCO * KS) void iaf_conv_kernel(ConvP p) 
                         pre1[i][r] = p.ql[cb + (size_t)r * HW];
                     }
                 }
-            } else if (EPI == EPI_HIDDEN) {
+            } else if (EPI == EPI_DGRAD_RES) {
+                if (p.mode == MODE_DGRAD_SKIP) {
+                    pre0[i] = *(const f32x4*)(p.zin + (size_t)Pl * p.cout + (cot0 + u) * 16 + 4 * kk);
+                    pre1[i] = *(const f32x4*)(p.skip + (size_t)Pl * p.cout + (cot0 + u) * 16 + 4 * kk);
+                }
+            } else if (EPI == EPI_HIDDEN || EPI == EPI_RES) {
+                if (EPI == EPI_RES && p.skip) pre2[i] = *(const f32x4*)(p.skip + (size_t)Pl * p.cout + (cot0 + u) * 16 + 4 * kk);
                 pbias[i] = *(const f32x4*)(p.bias + (cot0 + u) * 16 + 4 * kk);
                 if (p.ctx) {
                     const size_t cb = ((size_t)bimg * p.cout + (cot0 + u) * 16 + 4 * kk) * HW + pp;
@@ -662,6 +681,39 @@ __global__ __launch_bounds__(64 * PXT * WCO * KS) void iaf_conv_kernel(ConvP p) 
                     const size_t cb = ((size_t)bimg * p.cout + co) * HW + pp;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) p.out0[cb + (size_t)r * HW] = v[r] + pre0[i][r] * __expf(-pre1[i][r]);
+                }
+            } else if (EPI == EPI_RES) {      // the arithmetic of iaf_conv_epilogue.hpp's EPI_RES
+                const int co = (cot0 + u) * 16 + 4 * kk;
+                f32x4 v = val[i] + pbias[i];
+                if (NTP == NTAPS && p.border) {
+#pragma unroll
+                    for (int t = 1; t < NTP; ++t)
+                        if (outside & (1u << t)) v += *(const f32x4*)(p.border + (size_t)(t - 1) * p.cout + co);
+                }
+                if (p.ctx) {
+                    if (p.ctx2) v += (pre0[i] + pre1[i]);
+                    else v += pre0[i];
+                }
+                if (p.skip) v = pre2[i] + 0.1f * v;                           // h_{i+1} = h_i + 0.1 conv2(.)  (ar.py:441)
+                *(f32x4*)(p.y + (size_t)Pl * p.cout + co) = v;
+                if (p.y2) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = elu_f(v[r]);
+                    *(f32x4*)(p.y2 + (size_t)Pl * p.cout + co) = v;
+                }
+            } else if (EPI == EPI_DGRAD_RES) {
+                const int co = (cot0 + u) * 16 + 4 * kk;
+                f32x4 v = val[i];
+                if (p.mode == MODE_DGRAD_SKIP) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = pre1[i][r] + v[r] * (pre0[i][r] > 0.f ? 1.f : pre0[i][r] + 1.f);
+                }
+                *(f32x4*)(p.y + (size_t)Pl * p.cout + co) = v;               // (may be p.skip itself: one lane reads and writes an element)
+                if (p.y2) *(f32x4*)(p.y2 + (size_t)Pl * p.cout + co) = 0.1f * v;
+                if (p.out0) {
+                    const size_t cb = ((size_t)bimg * p.cout + co) * HW + pp;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) p.out0[cb + (size_t)r * HW] = v[r];
                 }
             } else if (EPI == EPI_HIDDEN) {
                 const int co = (cot0 + u) * 16 + 4 * kk;

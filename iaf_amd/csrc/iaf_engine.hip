@@ -140,6 +140,9 @@ struct RangeWord {
 struct iaf_stack : PackState {     // precision (forward convs: F32 = the exact fp32 MFMA, else split products), packs, f16_off, prepared
     int n_z, n_h, depth_ar, variant;
     int nlayers;          // depth_ar + 1
+    int resnet = 0;       // iaf_stack_create_resnet: residual blocks of the masked ResNet (ar.py:478-528), 0 = the plain conv stack.  Such a
+                          // stack has depth_ar = 2 resnet + 1 hidden convs -- L[0] the input conv, L[2i+1] / L[2i+2] conv1 / conv2 of block i --
+                          // so everything that walks L[] (prepare, packs, weight gradients, weight norm, work counts) serves it unchanged
     GemmLayer L[MAX_GEMM_LAYERS];
     GemmLayer T[MAX_GEMM_LAYERS];   // transposed problems (dX = W^T dY) of the same layers; valid when training
     bool training = false;
@@ -574,6 +577,22 @@ extern "C" int iaf_stack_create(iaf_stack_t** out, int n_z, int n_h, int depth_a
     return IAF_OK;
 }
 
+// The masked ResNet of the reference's deep IAF (graphy/nodes/ar.py:428-448, 478-528; models.py 'down_iaf2_deep'): the same object with
+// 2 depth + 1 hidden convs and the residual launch sequence (run_resnet, iaf_step_forward_train, iaf_step_backward).
+extern "C" int iaf_stack_create_resnet(iaf_stack_t** out, int n_z, int n_h, int depth, int variant) {
+    if (!out) return IAF_ERR_NULL;
+    *out = nullptr;
+    if (n_z <= 0 || n_h <= 0 || depth < 1 || 2 * depth + 2 > MAX_GEMM_LAYERS) return IAF_ERR_SHAPE;
+    if (variant != IAF_VARIANT_THEANO) return IAF_ERR_UNSUPPORTED;     // (resnet_layer_a passes no flipmask, ar.py:434-435: only the plain ordering exists)
+    if (!(n_z % n_h == 0 || n_h % n_z == 0)) return IAF_ERR_NOT_MULTIPLE;
+    if (n_z % 16 != 0 || n_h % 16 != 0 || n_z > 16 * PREP_MAXI || n_h > 16 * PREP_MAXI) return IAF_ERR_UNSUPPORTED;
+    iaf_stack_t* s = nullptr;
+    if (int rc = iaf_stack_create(&s, n_z, n_h, 2 * depth + 1, variant)) return rc;
+    s->resnet = depth;
+    *out = s;
+    return IAF_OK;
+}
+
 static void prof_free(iaf_stack* s) {
     for (int i = 0; i < s->prof_cap; ++i) {
         if (s->prof_start) (void)hipEventDestroy(s->prof_start[i]);
@@ -657,6 +676,7 @@ static int xch_reset_sets(iaf_stack_t* s) {
 
 extern "C" int iaf_stack_set_halo_exchange(iaf_stack_t* s, int on) {
     if (!s) return IAF_ERR_NULL;
+    if (s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h)
     s->xch_on = on != 0;
     return xch_reset_sets(s);                                // a fresh start either way: error words cleared
 }
@@ -676,6 +696,7 @@ extern "C" int iaf_stack_get_free_bits_groups(const iaf_stack_t* s, int* groups)
 
 extern "C" int iaf_stack_set_halo_exchange_debug(iaf_stack_t* s, unsigned knobs) {
     if (!s) return IAF_ERR_NULL;
+    if (s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h)
     s->xch_knob = knobs;
     return IAF_OK;
 }
@@ -720,7 +741,7 @@ extern "C" int iaf_stack_set_precision(iaf_stack_t* s, int precision) {
     if (precision != IAF_PRECISION_F32 && precision != IAF_PRECISION_BF16X3 && precision != IAF_PRECISION_F16X2) return IAF_ERR_SHAPE;
     bool new_pack = false;
     if (precision == IAF_PRECISION_F16X2) {
-        if (s->generic) return IAF_ERR_UNSUPPORTED;
+        if (s->generic || s->resnet) return IAF_ERR_UNSUPPORTED;      // (masked ResNet: no kernel of its launch sequence reads fp16 planes)
         for (int l = 0; l < s->nlayers; ++l) if (!s->L[l].wp3) return IAF_ERR_UNSUPPORTED;      // (c_in % 32: the same fragments, two planes)
         if (int rc = s->rng.alloc()) return rc;
         for (int l = 0; l < s->nlayers; ++l) {
@@ -744,14 +765,34 @@ static inline void stack_prep_packs(const iaf_stack_t* s, const GemmLayer& L, Pr
     prep_layer_packs(P, L, pack_prep_writes(*s, PACK_STACK, f16_active(s), L.wp3 != nullptr, s->training), s->rng.dev);
 }
 
+// the forward epilogue of layer l: the output pair; in a masked ResNet the input conv and every block's conv2 write the residual stream
+static int layer_epi(const iaf_stack_t* s, int l) {
+    return l == s->depth_ar ? EPI_OUT : (s->resnet && l % 2 == 0) ? EPI_RES : EPI_HIDDEN;
+}
+
 extern "C" int iaf_stack_get_precision(const iaf_stack_t* s, int layer, int B, int H, int W) {
     if (!s || layer < 0 || layer >= s->nlayers) return IAF_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0) return IAF_ERR_SHAPE;
     GemmLayer t = s->L[layer];
     const bool is_out = (layer == s->depth_ar);
     // what a forward launch of this layer at this size will run (same decision function as the launch)
-    return bf3_select(s, t, is_out ? EPI_OUT : EPI_HIDDEN, false, !(is_out && s->depth_ar == 0) && (layer > 0 || !is_out),
+    return bf3_select(s, t, layer_epi(s, layer), false, !(is_out && s->depth_ar == 0) && (layer > 0 || !is_out),
                       (long long)B * H * W, W) ? IAF_PRECISION_BF16X3 : IAF_PRECISION_F32;
+}
+
+// the epilogue of layer l's data gradient (iaf_step_backward's walk): layer 0 ends in dz; in a masked ResNet the output pair and every
+// block's conv1 write the residual stream's gradient
+static int layer_dgrad_epi(const iaf_stack_t* s, int l) {
+    return (s->resnet && l > 0 && (l == s->depth_ar || (l & 1))) ? EPI_DGRAD_RES : EPI_DGRAD;
+}
+
+extern "C" int iaf_stack_get_dgrad_precision(const iaf_stack_t* s, int layer, int B, int H, int W) {
+    if (!s || layer < 0 || layer >= s->nlayers) return IAF_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0) return IAF_ERR_SHAPE;
+    if (!s->training || s->generic) return IAF_ERR_NOT_PREPARED;
+    GemmLayer t = s->T[layer];
+    // what iaf_step_backward's data-gradient launch of this layer at this size will run (same decision function as the launch)
+    return bf3_select(s, t, layer_dgrad_epi(s, layer), true, true, (long long)B * H * W, W) ? IAF_PRECISION_BF16X3 : IAF_PRECISION_F32;
 }
 
 extern "C" int iaf_stack_set_tuning_bf3(iaf_stack_t* s, int layer, int nt, int ppw, int pxt, int ks, int wco) {
@@ -948,14 +989,14 @@ extern "C" size_t iaf_stack_workspace_bytes(const iaf_stack_t* s, int B, int H, 
     const size_t P = (size_t)B * H * W;
     // two ping-pong hidden buffers [P][n_h], kl elements [B,n_z,H,W], row sums [B*n_z]
     size_t bytes = 0;
-    if (s->depth_ar > 0) bytes += 2 * align_up(P * s->n_h * sizeof(float), 256);
+    if (s->depth_ar > 0) bytes += (s->resnet ? 3 : 2) * align_up(P * s->n_h * sizeof(float), 256);      // (masked ResNet: raw stream, elu(stream), t_i)
     bytes += align_up(P * s->n_z * sizeof(float), 256);
     bytes += align_up((size_t)B * s->n_z * sizeof(float), 256);
     return bytes;
 }
 
 struct Ws {
-    float* hbuf[2];
+    float* hbuf[3];       // [2]: masked ResNet only
     float* kl_elem;
     float* rowsum;
 };
@@ -965,10 +1006,11 @@ static int carve_ws(const iaf_stack_t* s, int B, int H, int W, void* ws, size_t 
     if (((uintptr_t)ws & 15) != 0 || ws_bytes < iaf_stack_workspace_bytes(s, B, H, W)) return IAF_ERR_WORKSPACE;
     const size_t P = (size_t)B * H * W;
     char* p = (char*)ws;
-    o->hbuf[0] = o->hbuf[1] = nullptr;
+    o->hbuf[0] = o->hbuf[1] = o->hbuf[2] = nullptr;
     if (s->depth_ar > 0) {
         o->hbuf[0] = (float*)p; p += align_up(P * s->n_h * sizeof(float), 256);
         o->hbuf[1] = (float*)p; p += align_up(P * s->n_h * sizeof(float), 256);
+        if (s->resnet) { o->hbuf[2] = (float*)p; p += align_up(P * s->n_h * sizeof(float), 256); }
     }
     o->kl_elem = (float*)p; p += align_up(P * s->n_z * sizeof(float), 256);
     o->rowsum = (float*)p;
@@ -1067,8 +1109,9 @@ static bool auto_shape_bf3(GemmLayer& L, bool is_out, long long P, int W) {
 // will a forward launch of this layer run the bf16x3 kernel?  (also fixes L.b_* to the shape it will use)
 static bool bf3_select(const iaf_stack_t* s, GemmLayer& L, int epi, bool negate_taps, bool pix_input, long long P, int W) {
     if (!prec_split(s) || !L.wp3 || !(s->packs & IAF_PACK_BF16X3)) return false;        // (iaf_stack_set_packs: the bf16x3 pack is not kept up to date)
-    if (negate_taps != (epi == EPI_DGRAD)) return false;           // mirrored taps: the data gradient (transposed bf16x3 pack), only
-    if (!(epi == EPI_HIDDEN || ((epi == EPI_OUT || epi == EPI_DGRAD) && pix_input))) return false;
+    const bool dgrad = (epi == EPI_DGRAD || epi == EPI_DGRAD_RES);
+    if (negate_taps != dgrad) return false;                        // mirrored taps: the data gradient (transposed bf16x3 pack), only
+    if (!(epi == EPI_HIDDEN || epi == EPI_RES || ((epi == EPI_OUT || dgrad) && pix_input))) return false;
     if (!L.b_user_tuned && L.tuned_P == P && L.tuned_W == W) {       // measured for exactly this problem size
         if (!L.tuned_bf3) return false;
         L.b_nt = L.t_nt; L.b_ppw = L.t_ppw; L.b_pxt = L.t_pxt; L.b_ks = L.t_ks; L.b_wco = L.t_wco;
@@ -1311,7 +1354,7 @@ static step_fn_t fused_step_plan(const iaf_stack_t* s, int B, int H, int W, int*
                                  bool launching = false) {
     static const int env = getenv("IAF_FUSE_STEP") ? atoi(getenv("IAF_FUSE_STEP")) : -1;       // dev knob: 0 / 1
     const int mode = env >= 0 ? env : s->fuse_step;
-    if (!mode || s->generic || !prec_split(s)) return nullptr;
+    if (!mode || s->generic || s->resnet || !prec_split(s)) return nullptr;      // (the masked ResNet runs layer by layer: run_resnet)
     if (s->depth_ar < 1 || s->depth_ar > 4 || (s->n_h & 15) || (s->n_z & 15)) return nullptr;
     if (s->fuse_first == 1) return nullptr;                  // the caller asked for the layer-by-layer variant with a fused first conv
     for (int l = 0; l < s->nlayers; ++l)                      // ... or pinned a per-layer launch shape: the layer-by-layer path is meant
@@ -1535,9 +1578,50 @@ static int launch_kl_from_parts(const float* part, float* rowsum, float* kl_obj,
     return (int)hipGetLastError();
 }
 
+// The masked ResNet (ar.py:478-528), layer by layer; D = s->resnet blocks:
+//   L[0]      EPI_RES     z (NCHW) -> h_0 = conv + context (raw)          and elu(h_0)
+//   L[2i+1]   EPI_HIDDEN  elu(h_i) -> t_i = elu(conv1)
+//   L[2i+2]   EPI_RES     t_i      -> h_{i+1} = h_i + 0.1 conv2 (raw)     and elu(h_{i+1}) unless i = D - 1
+//   L[2D+1]   EPI_OUT     h_D (raw)  -> the (mean, logsd) pair under base.mode
+// raw: the stream, updated in place (an element is read and written by one lane); h_last: where h_D goes (raw itself when evaluating).
+// Evaluation: act, t are two scratch buffers, save == NULL.  Training: save[l] = what layer l + 1 reads, the activations the backward
+// pass needs: save[2i] = elu(h_i), save[2i+1] = t_i, save[2D] = h_D.
+static int run_resnet(iaf_stack_t* s, const ConvP& base, const float* ctx, const float* ctx2, float* raw, float* h_last, float* act,
+                      float* t, float* const* save, hipStream_t st) {
+    const int D = s->resnet;
+    int rc;
+    ConvP p = base;
+    p.mode = 0;
+    p.ctx = ctx; p.ctx2 = ctx2;
+    p.y = raw; p.y2 = save ? save[0] : act;
+    if ((rc = launch_gemm(s, s->L[0], EPI_RES, false, 0, p, IN_NCHW, st))) return rc;
+    for (int i = 0; i < D; ++i) {
+        const bool last = (i == D - 1);
+        const float* a_i = save ? save[2 * i] : act;
+        float* t_i = save ? save[2 * i + 1] : t;
+        p = base;
+        p.mode = 0;
+        p.x = a_i; p.y = t_i;
+        if ((rc = launch_gemm(s, s->L[2 * i + 1], EPI_HIDDEN, false, 2 * i + 1, p, IN_PIXMAJOR, st))) return rc;
+        p = base;
+        p.mode = 0;
+        p.x = t_i; p.skip = raw;
+        p.y = last ? h_last : raw;
+        p.y2 = last ? nullptr : (save ? save[2 * i + 2] : act);
+        if ((rc = launch_gemm(s, s->L[2 * i + 2], EPI_RES, false, 2 * i + 2, p, IN_PIXMAJOR, st))) return rc;
+    }
+    p = base;
+    p.x = h_last;
+    return launch_gemm(s, s->L[s->depth_ar], EPI_OUT, false, s->depth_ar, p, IN_PIXMAJOR, st);
+}
+
 static int run_stack(iaf_stack_t* s, ConvP base, int first_inmode, const float* ctx, const float* ctx2, const Ws& ws,
                      hipStream_t st) {
     if (s->generic) return run_stack_generic(s, base, first_inmode, ctx, ctx2, ws, st);
+    if (s->resnet) {
+        if (first_inmode != IN_NCHW) return IAF_ERR_UNSUPPORTED;
+        return run_resnet(s, base, ctx, ctx2, ws.hbuf[0], ws.hbuf[0], ws.hbuf[1], ws.hbuf[2], nullptr, st);
+    }
     if (first_inmode == IN_NCHW || first_inmode == IN_POSTERIOR) {
         int R = 0;
         size_t lds = 0;
@@ -1575,6 +1659,7 @@ static int time_reps(hipStream_t st, int reps, float* avg_ms, F&& launch) {
 extern "C" int iaf_step_time_layer(iaf_stack_t* s, int layer, const float* z, const float* context, float* z_new,
                                    float* logsd, int B, int H, int W, void* workspace, size_t workspace_bytes, int reps,
                                    void* stream, float* avg_ms) {
+    if (s && s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h; before any other answer)
     int rc = check_dims(s, B, H, W);
     if (rc) return rc;
     if (!z || !z_new || !logsd || !avg_ms || (s->depth_ar > 0 && !context)) return IAF_ERR_NULL;
@@ -1624,6 +1709,7 @@ extern "C" int iaf_step_time_layer(iaf_stack_t* s, int layer, const float* z, co
 extern "C" int iaf_stack_autotune(iaf_stack_t* s, const float* z, const float* context, float* z_new, float* logsd, int B,
                                   int H, int W, void* workspace, size_t workspace_bytes, int reps, void* stream,
                                   int* chosen, float* us) {
+    if (s && s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h; before any other answer)
     int rc = check_dims(s, B, H, W);
     if (rc) return rc;
     if (s->generic) return IAF_OK;
@@ -1753,6 +1839,7 @@ extern "C" int iaf_stack_autotune(iaf_stack_t* s, const float* z, const float* c
 
 extern "C" int iaf_stack_set_packs(iaf_stack_t* s, int packs) {
     if (!s) return IAF_ERR_NULL;
+    if (s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h)
     PackFacts f;
     f.generic = s->generic; f.training = s->training; f.f16_active = f16_active(s);
     f.all_split = true;            // only a stack whose every layer has a bf16x3 pack can do without the fp32 one
@@ -1762,6 +1849,7 @@ extern "C" int iaf_stack_set_packs(iaf_stack_t* s, int packs) {
 
 extern "C" int iaf_stack_set_fuse_step(iaf_stack_t* s, int mode) {
     if (!s) return IAF_ERR_NULL;
+    if (s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h)
     if (mode < 0 || mode > 2) return IAF_ERR_SHAPE;
     s->fuse_step = mode;
     return IAF_OK;
@@ -1776,6 +1864,7 @@ extern "C" int iaf_stack_step_is_fused(const iaf_stack_t* s, int B, int H, int W
 
 extern "C" int iaf_stack_set_fuse_first(iaf_stack_t* s, int mode) {
     if (!s) return IAF_ERR_NULL;
+    if (s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h)
     if (mode < 0 || mode > 2) return IAF_ERR_SHAPE;
     s->fuse_first = mode;
     return IAF_OK;
@@ -1902,6 +1991,7 @@ extern "C" int iaf_posterior_block_forward(iaf_stack_t* s, const float* qz_mean,
                                            const float* down_context, const float* eps, float kl_min, float* z_out,
                                            float* kl_obj, float* kl_cost, float* kl_elem, int B, int H, int W,
                                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (s && s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h; before any other answer)
     int rc = check_dims(s, B, H, W);
     if (rc) return rc;
     if (!qz_mean || !qz_logsd || !rz_mean || !rz_logsd || !pz_mean || !pz_logsd || !eps || !z_out || !kl_obj ||
@@ -2132,6 +2222,8 @@ extern "C" int iaf_step_forward_train(iaf_stack_t* s, const float* z, const floa
     base.zin = z; base.out0 = z_new; base.out1 = logsd; base.mode = MODE_IAF;
     base.x = z;
     if (s->generic) { Ws none; memset(&none, 0, sizeof(none)); return run_stack_generic(s, base, IN_NCHW, context, nullptr, none, st, tw.h); }
+    // masked ResNet: the stream lives in da[0] (free until the backward pass), h_D and what every conv reads in h[] (run_resnet)
+    if (s->resnet) return run_resnet(s, base, context, nullptr, tw.da[0], tw.h[2 * s->resnet], nullptr, nullptr, tw.h, st);
     {   // the one-launch step, writing the hidden activations of the owned rows where the backward expects them
         int R = 0;
         size_t lds = 0;
@@ -2384,16 +2476,27 @@ extern "C" int iaf_step_backward(iaf_stack_t* s, const float* z, const float* co
         const float* x_in = (l == 0) ? tw.zpm : tw.h[l - 1];     // what layer l read in the forward pass
         ConvP p = base;
         p.x = dy;
+        const int epi = layer_dgrad_epi(s, l);
         if (l == 0) {                               // dz = W_0^T dY + dz_new e^{-logsd}
             p.mode = MODE_DGRAD_Z;
             p.qm = dz_new; p.ql = logsd; p.out0 = dz;
+        } else if (s->resnet && l == d) {           // masked ResNet: the output pair read the RAW stream: d h_D = W_out^T dY -> da[0], the
+                                                    // stream's gradient from here on (updated in place); 0.1 d h_D = dY of the last conv2
+            p.mode = MODE_DGRAD_RAW;
+            p.y = tw.da[0]; p.y2 = tw.da[l - 1];
+        } else if (s->resnet && (l & 1)) {          // conv1 of block i = (l - 1) / 2: d h_i = d h_{i+1} + elu'(h_i) (W^T d t_i); 0.1 d h_i = dY
+                                                    // of block i - 1's conv2; block 0: d h_0 is the input conv's dY itself, and d context
+            p.mode = MODE_DGRAD_SKIP;
+            p.zin = tw.h[l - 1]; p.skip = tw.da[0];
+            p.y = tw.da[0]; p.y2 = (l > 1) ? tw.da[l - 1] : nullptr;
+            p.out0 = (l == 1) ? dcontext : nullptr;
         } else {                                    // d a_{l-1} = (W_l^T dY) elu'(h_{l-1})   (+ NCHW copy = d context)
             p.mode = MODE_DGRAD_ELU;
             p.zin = tw.h[l - 1];
             p.y = tw.da[l - 1];
             p.out0 = (l - 1 == 0) ? dcontext : nullptr;
         }
-        if ((rc = launch_gemm(s, s->T[l], EPI_DGRAD, true, -1, p, IN_PIXMAJOR, st))) return rc;
+        if ((rc = launch_gemm(s, s->T[l], epi, true, -1, p, IN_PIXMAJOR, st))) return rc;
         if ((rc = launch_wgrad(s, s->L[l], x_in, dy, tw.part[l], tapmask, B, H, W, st, tap_sign, prec_split(s)))) return rc;
         reduce_add(l, dy);
         if (l == d) {
@@ -2495,6 +2598,7 @@ extern "C" int iaf_posterior_block_forward_train(iaf_stack_t* s, const float* qz
                                                  const float* pz_logsd, const float* up_context, const float* down_context,
                                                  const float* eps, float kl_min, float* z_out, float* kl_obj, float* kl_cost,
                                                  int B, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
+    if (s && s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h; before any other answer)
     int rc = check_dims(s, B, H, W);
     if (rc) return rc;
     if (!s->training) return IAF_ERR_NOT_PREPARED;
@@ -2560,6 +2664,7 @@ extern "C" int iaf_posterior_block_backward(iaf_stack_t* s, const float* qz_mean
                                             float* dpz_logsd, float* dcontext, const float* const* V, const float* const* g,
                                             float* const* dV, float* const* dg, float* const* db, int B, int H, int W,
                                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (s && s->resnet) return IAF_ERR_UNSUPPORTED;      // (iaf_stack_create_resnet: include/iaf_hip.h; before any other answer)
     int rc = check_dims(s, B, H, W);
     if (rc) return rc;
     if (!s->training) return IAF_ERR_NOT_PREPARED;
@@ -2597,6 +2702,8 @@ extern "C" int iaf_layer_work(const iaf_stack_t* s, int layer, int B, int H, int
     if (bytes) {
         double b = 4.0 * px * L.cin;                                     // activations in
         if (layer == s->depth_ar) b += 4.0 * px * (3.0 * s->n_z);         // z in, z_new out, logsd out
+        else if (s->resnet && layer % 2 == 0)                             // EPI_RES: raw stream out, context (layer 0) or skip in, and
+            b += 4.0 * px * L.cout * (layer == s->depth_ar - 1 ? 2.0 : 3.0);   // elu(stream) out unless the block is the last
         else b += 4.0 * px * L.cout * (layer == 0 ? 2.0 : 1.0);           // hidden out (+ context in)
         b += 4.0 * ((double)L.nchunk * NTAPS * L.ncot * 256 + L.cout);    // packed weights + bias, once
         *bytes = b;

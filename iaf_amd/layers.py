@@ -127,7 +127,7 @@ class ARStack(object):
             raise ValueError("the gfx950 engine implements the (mean, logsd) output pair n_out=[n_z, n_z]")
         self.n_z, self.n_h_list, self.depth_ar = int(n_z), n_h, len(n_h)
         self.n_h = int(n_h[0]) if n_h else int(n_z)
-        self._own = _capi.Handle("iaf_stack_create", self.n_z, self.n_h, self.depth_ar, variant)
+        self._own = self._create()
         self._h = self._own.h
         if os.environ.get("IAF_PRECISION"):          # process-wide override of the default (bf16x3): "f32" | "bf16x3"
             self.set_precision(os.environ["IAF_PRECISION"])
@@ -135,9 +135,16 @@ class ARStack(object):
         self._prep_key = None
         self._keepalive = None
 
+    def _create(self):
+        return _capi.Handle("iaf_stack_create", self.n_z, self.n_h, self.depth_ar, self.variant)
+
     # -- weights -------------------------------------------------------------------------------
     def conv_names(self):
         return ["layer_%d" % i for i in range(self.depth_ar)] + ["layer_out_0", "layer_out_1"]
+
+    def _theano_bases(self):
+        """per conv in engine order, the reference's variable name relative to the stack's (ar.py:388-395)"""
+        return ["%d" % i for i in range(self.depth_ar)] + ["out_0", "out_1"]
 
     def prepare(self, params, force=False):
         """params: {"layer_0/V": tensor, "layer_0/g": ..., "layer_out_1/b": ...} (device fp32).
@@ -164,11 +171,12 @@ class ARStack(object):
         tens = []
         theano = self.variant in (_capi.IAF_VARIANT_THEANO, _capi.IAF_VARIANT_THEANO_FLIPMASK)
         names = self.conv_names()
+        bases = self._theano_bases() if theano else None
         for ci, nm in enumerate(names):
             n_in = sizes[min(ci, self.depth_ar)]
             n_out = sizes[ci + 1] if ci < self.depth_ar else self.n_z
             if theano:
-                base = ("%d" % ci) if ci < self.depth_ar else ("out_%d" % (ci - self.depth_ar))
+                base = bases[ci]
                 V, g, b = params[base + "_w"], params[base + "_s"], params[base + "_b"]
                 _check_act(V, base + "_w", (n_out, n_in + 1, 3, 3))
             else:
@@ -182,8 +190,7 @@ class ARStack(object):
     def _grad_keys(self):
         """per conv, the keys its (V, g, b) slots go by in a params / grads dict (see _param_tensors)"""
         if self.variant in (_capi.IAF_VARIANT_THEANO, _capi.IAF_VARIANT_THEANO_FLIPMASK):
-            bases = ["%d" % i for i in range(self.depth_ar)] + ["out_0", "out_1"]
-            return [(b + "_w", b + "_s", b + "_b") for b in bases]
+            return [(b + "_w", b + "_s", b + "_b") for b in self._theano_bases()]
         return [(nm + "/V", nm + "/g", nm + "/b") for nm in self.conv_names()]
 
     def time_layer(self, layer, z, context, reps=50):
@@ -221,6 +228,14 @@ class ARStack(object):
         """what a forward launch of GEMM layer `layer` at this size will run: "bf16x3" or "f32" (layers the bf16x3 kernels
         do not cover, or small launches they do not speed up, stay on the fp32 kernel)"""
         code = _capi.lib().iaf_stack_get_precision(self._h, int(layer), int(B), int(H), int(W))
+        if code < 0:
+            _capi.check(code)
+        return "bf16x3" if code == _capi.IAF_PRECISION_BF16X3 else "f32"
+
+    def dgrad_precision(self, layer, B, H, W):
+        """what the data-gradient launch of GEMM layer `layer` in iaf_step_backward will run at this size: "bf16x3" or "f32"
+        (training mode only: iaf_stack_get_dgrad_precision)"""
+        code = _capi.lib().iaf_stack_get_dgrad_precision(self._h, int(layer), int(B), int(H), int(W))
         if code < 0:
             _capi.check(code)
         return "bf16x3" if code == _capi.IAF_PRECISION_BF16X3 else "f32"
@@ -556,6 +571,32 @@ class ARStack(object):
 
 
 RESAMPLE_MODES = {"down_even": 0, "down_odd": 1, "up_nearest": 2, "up_zero_odd": 3, "up_zero_even": 4, "down_sum4": 5}
+
+
+class ResnetARStack(ARStack):
+    """The masked ResNet of the reference's deep IAF, N.ar.resnet (graphy/nodes/ar.py:428-448, 478-528), bound to an engine handle
+    (iaf_stack_create_resnet): h_0 = conv_input(z) + context; `depth` blocks h <- h + 0.1 conv2(elu(conv1(elu(h)))); the (mean, logsd)
+    pair on the raw h.  Theano statement, plain ordering, elu, layertype 'a'; channel counts multiples of 16.
+
+    To the engine it is a stack of 2 depth + 1 hidden convs (layer 0 = the input conv, 2i+1 / 2i+2 = conv1 / conv2 of block i), which
+    is what depth_ar, layer_work, layer_precision and set_tuning_bf3 count in; `depth` is the reference's.  prepare() reads
+    "input_w|_s|_b", "<i>_conv1_...", "<i>_conv2_...", "out_0_...", "out_1_..." relative to the stack's name (ar.py:483-498).  Every
+    method of ARStack serves it except the posterior block, autotune / time_layer and the fuse, exchange and pack knobs, which raise
+    UnsupportedError (include/iaf_hip.h)."""
+
+    def __init__(self, n_z, n_h, depth):
+        self.depth = int(depth)
+        ARStack.__init__(self, n_z, [int(n_h)] * (2 * self.depth + 1), variant=_capi.IAF_VARIANT_THEANO)
+
+    def _create(self):
+        return _capi.Handle("iaf_stack_create_resnet", self.n_z, self.n_h, self.depth, self.variant)
+
+    def conv_names(self):
+        return self._theano_bases()
+
+    def _theano_bases(self):
+        blocks = [b for i in range(self.depth) for b in ("%d_conv1" % i, "%d_conv2" % i)]
+        return ["input"] + blocks + ["out_0", "out_1"]
 
 
 def resample2(x, mode):
@@ -1240,6 +1281,40 @@ def multiconv2d(name, n_in, n_h, n_out, size_kernel=(3, 3), flipmask=False, nl="
     def f(h, context, w, return_hiddens=False):
         if return_hiddens:
             raise ValueError("hidden activations stay on chip; return_hiddens is not available")
+        rel = {k[len(name) + 1:]: v for k, v in w.items() if k.startswith(name + "_")}
+        stack.prepare(rel)
+        return stack.ar_multiconv2d(h, context)
+
+    return _Struct(f=f, w=w, stack=stack, postup=lambda updates, w: updates)
+
+
+def resnet(name, depth, n_in, n_h, n_out, size_kernel=(3, 3), flipmask=False, nl="elu", layertype="a", factor=4, weightsharing=False,
+           w=None):
+    """Mirror of N.ar.resnet (graphy/nodes/ar.py:478-528) with layertype 'a' (resnet_layer_a, :428-448), as constructed at
+    models.py:104-108 for 'down_iaf2_deep': returns a callable struct `f(h, context, w)` -> [out_0, out_1] reading
+    w[name+'_input_w'|'_b'|'_s'], w[name+'_<i>_conv1_...'], w[name+'_<i>_conv2_...'] and w[name+'_out_<j>_...']."""
+    if isinstance(n_out, int):
+        n_out = [n_out]
+    if flipmask:
+        raise _capi.UnsupportedError("resnet: flipmask=True is not built (resnet_layer_a passes no flipmask to its convs, ar.py:434-435: "
+                                     "a flipped deep network is inconsistent in the reference itself)")
+    if layertype != "a":
+        raise _capi.UnsupportedError("resnet: layertype %r is not built (only 'a', the two 3x3 convs of ar.py:428-448)" % (layertype,))
+    if weightsharing:
+        raise _capi.UnsupportedError("resnet: weight sharing between the blocks is not built")
+    if not _is_elu(nl):
+        raise _capi.UnsupportedError("resnet: nl=%r is not built (the engine's epilogues apply elu)" % (nl,))
+    if tuple(size_kernel) != (3, 3):
+        raise _capi.UnsupportedError("resnet: size_kernel=%r is not built (3x3 only)" % (tuple(size_kernel),))
+    if list(n_out) != [n_in, n_in]:
+        raise _capi.UnsupportedError("resnet: the engine implements the (mean, logsd) output pair n_out=[n_in, n_in]")
+    stack = ResnetARStack(n_in, n_h, depth)
+
+    def f(h, context, w, return_hiddens=False):
+        if return_hiddens:
+            raise ValueError("hidden activations stay on chip; return_hiddens is not available")
+        if context is None:         # (ar.py:503 allows it; the engine's input conv always adds one)
+            raise _capi.UnsupportedError("resnet: h_context=None is not built: pass a context [B, n_h, H, W] (zeros for none)")
         rel = {k[len(name) + 1:]: v for k, v in w.items() if k.startswith(name + "_")}
         stack.prepare(rel)
         return stack.ar_multiconv2d(h, context)

@@ -16,6 +16,14 @@ context, the KL, concat([h_det, z]), and the two elementwise halves of the backw
 _backward_pre / _backward_post) that read their operands at channel offsets INSIDE the two conv outputs and write the gradients of the
 conv outputs whole: no split() copies, no torch.cat.
 
+'down_iaf2_deep' (models.py:104-108, 272-285) also has the channel layouts of 'down_iaf2_nl' and prior 'diag': ONE IAF step whose
+autoregressive network is the masked ResNet N.ar.resnet(name + '_deepiaf', depth_ar, n_z, n_h, [n_z, n_z]) (graphy/nodes/ar.py:428-448, 478-528)
+-- h_0 = conv_input(z) + context, depth_ar blocks h <- h + 0.1 conv2(elu(conv1(elu(h)))), the (mean, logsd) pair on the raw h -- on a
+layers.ResnetARStack; load() reads w[name + '_deepiaf_input_w|_s|_b'], '..._<i>_conv1_...', '..._<i>_conv2_...', '..._out_<j>_...'.  The
+step is 2 depth_ar + 2 launches of the conv kernels; around it are the chain's four elementwise launches with a second log-determinant
+(and, backwards, a second context gradient) of cached zeros, so down_q is capturable after a warm-up as the chain is.  depth_ar is 1 to 4,
+the ordering the plain one (flipmask=True: UnsupportedError), and prior 'made' with it raises ValueError.
+
 prior='made' (models.py:36-38, 304-309; with 'down_iaf2_nl' and 'down_iaf2_nl2') is the autoregressive prior: a further stack,
 <name>_prior_conv1 with the plain ordering, reads z and a context of its own, and down_conv1 emits that context in place of the prior's
 mean and log standard deviation:
@@ -41,9 +49,9 @@ import torch
 from . import _capi
 from .distributions import gaussian_diag_logps_logsd
 from .iaf_layer import gaussian_sample
-from .layers import ARStack, PrepBatch, kl_free_bits, split, theano_stack, _check_act, _ptr, _stream
+from .layers import ARStack, PrepBatch, ResnetARStack, kl_free_bits, split, theano_stack, _check_act, _ptr, _stream
 
-POSTERIORS = ("down_iaf2_nl", "up_iaf2_nl", "down_iaf2_nl2")
+POSTERIORS = ("down_iaf2_nl", "up_iaf2_nl", "down_iaf2_nl2", "down_iaf2_deep")
 PRIORS = ("diag", "made")
 
 
@@ -55,30 +63,35 @@ class CVAELayerIAF(object):
             raise Exception("Unknown posterior " + posterior)                     # models.py:115
         if prior == "made" and posterior == "up_iaf2_nl":
             raise ValueError("prior 'made' with posterior 'up_iaf2_nl' is not built: use 'down_iaf2_nl' or 'down_iaf2_nl2'")
+        if prior == "made" and posterior == "down_iaf2_deep":
+            raise ValueError("prior 'made' with posterior 'down_iaf2_deep' is not built: use prior 'diag'")
         self.name, self.n_h, self.n_z, self.depth_ar = name, int(n_h), int(n_z), int(depth_ar)
         self.posterior, self.kl_min, self.prior = posterior, float(kl_min), prior
+        self._st, self._rel, self._rel2, self._rel_p, self._zeros = None, None, None, None, {}
+        self.training = False
+        self.stack2, self._prep, self.prior_stack = None, None, None
+        if posterior == "down_iaf2_deep":
+            # models.py:104-108: N.ar.resnet(name + '_deepiaf', depth_ar, n_z, n_h, [n_z, n_z], kernel, False): depth_ar counts residual
+            # blocks here, and the ordering is always the plain one
+            if flipmask:
+                raise _capi.UnsupportedError("'down_iaf2_deep' has the plain ordering only (resnet_layer_a passes no flipmask, ar.py:434-435)")
+            self.stack = ResnetARStack(self.n_z, self.n_h, self.depth_ar)
+            return
         # With prior 'made', BOTH plain-ordering stacks (this one unless flipmask, and the prior's) may have channel counts that are not
         # multiples of 16 (n_z | n_h): theano_stack then returns an EmbeddedTheanoStack, which pads and slices with torch around
         # every step.  The flipped ordering does not embed: flipmask=True and 'down_iaf2_nl2' raise UnsupportedError at such sizes.
         self.stack = theano_stack(self.n_z, [self.n_h] * self.depth_ar,
                                   _capi.IAF_VARIANT_THEANO_FLIPMASK if flipmask else _capi.IAF_VARIANT_THEANO, embed=(prior == "made"))
         # the second flow of the chain is ALWAYS flipped (models.py:98 hard-codes True); `flipmask` is the first flow's
-        self.stack2, self._prep = None, None
         if posterior == "down_iaf2_nl2":
             if self.depth_ar < 1:
                 raise ValueError("'down_iaf2_nl2' needs depth_ar >= 1: both flows take the context through their first conv")
             self.stack2 = ARStack(self.n_z, [self.n_h] * self.depth_ar, variant=_capi.IAF_VARIANT_THEANO_FLIPMASK)
         # the MADE prior's stack always has the plain ordering (models.py:37 hard-codes False)
-        self.prior_stack = None
         if prior == "made":
             if self.depth_ar < 1:
                 raise ValueError("prior 'made' needs depth_ar >= 1: the prior's stack takes made_context through its first conv")
             self.prior_stack = theano_stack(self.n_z, [self.n_h] * self.depth_ar, _capi.IAF_VARIANT_THEANO, embed=True)
-        self._st = None
-        self.training = False
-        self._rel = None
-        self._rel2 = None
-        self._rel_p = None
 
     def set_training(self, on=True):
         """keep what backward() needs in up() / down_q() (call load() again afterwards: the data-gradient weight packs are
@@ -94,7 +107,7 @@ class CVAELayerIAF(object):
         """w: the reference's parameter dict; reads w[name + '_posterior_conv1_<i>_w|_b|_s'] and '..._out_<i>_...', for
         'down_iaf2_nl2' also w[name + '_posterior_conv2_...'], for prior 'made' also w[name + '_prior_conv1_...'] (all stacks
         prepared in ONE launch)"""
-        pre = self.name + "_posterior_conv1_"
+        pre = self.name + ("_deepiaf_" if self.posterior == "down_iaf2_deep" else "_posterior_conv1_")
         self._rel = {k[len(pre):]: v for k, v in w.items() if k.startswith(pre)}
         if self.stack2 is None and self.prior_stack is None:
             self.stack.prepare(self._rel)
@@ -118,7 +131,7 @@ class CVAELayerIAF(object):
         """h: output of up_conv1 [B, 2 n_h + 2 n_z, H, W].  Returns the input of up_conv2 (before its nonlinearity):
         h_det for 'down_iaf2_nl' (models.py:180-182), concat([h_det, z]) for 'up_iaf2_nl' (:168-176; needs eps)."""
         n_h, n_z = self.n_h, self.n_z
-        if self.posterior == "down_iaf2_nl2" or self.prior == "made":
+        if self.posterior in ("down_iaf2_nl2", "down_iaf2_deep") or self.prior == "made":
             # as 'down_iaf2_nl' (models.py:179-181); the chain's kernels read the conv output itself, so what is kept of it are views
             _check_act(h, "h (up_conv1 output)")
             if h.dim() != 4 or h.shape[1] != 2 * n_h + 2 * n_z:
@@ -148,7 +161,7 @@ class CVAELayerIAF(object):
         n_h, n_z, st = self.n_h, self.n_z, self._st
         if self.prior == "made":
             return self._down_q_made(h, eps)
-        if self.posterior == "down_iaf2_nl2":
+        if self.posterior in ("down_iaf2_nl2", "down_iaf2_deep"):
             return self._down_q_chain(h, eps)
         if self.posterior == "down_iaf2_nl":
             h_det, pz_mean, pz_logsd, rz_mean, rz_logsd, down_context = split(h, 1, [n_h, n_z, n_z, n_z, n_z, n_h])
@@ -186,7 +199,7 @@ class CVAELayerIAF(object):
         if st is None or "up_conv1" not in st:
             raise RuntimeError("down_q() follows up()")
         if eps is None:
-            raise ValueError("'down_iaf2_nl2' samples the posterior in the down pass: pass eps")
+            raise ValueError("'%s' samples the posterior in the down pass: pass eps" % self.posterior)
         up = st["up_conv1"]
         B, H, W = int(up.shape[0]), int(up.shape[2]), int(up.shape[3])
         _check_act(h, "h (down_conv1 output)", (B, 2 * n_h + 4 * n_z, H, W))
@@ -196,7 +209,10 @@ class CVAELayerIAF(object):
         _capi.check(_capi.lib().iaf_chain_head(_ptr(up), _ptr(h), _ptr(eps), _ptr(z0), _ptr(logq0), _ptr(context), B, n_h, n_z, H * W,
                                                _stream()))
         z1, s1 = (self.stack.iaf_step_train if self.training else self.stack.iaf_step)(z0, context)       # :281-285
-        z2, s2 = (self.stack2.iaf_step_train if self.training else self.stack2.iaf_step)(z1, context)     # :286-291
+        if self.stack2 is not None:
+            z2, s2 = (self.stack2.iaf_step_train if self.training else self.stack2.iaf_step)(z1, context)     # :286-291
+        else:       # 'down_iaf2_deep': ONE flow; the chain's tail adds a second log-determinant of zeros (x + 0 is x, bit for bit)
+            z2, s2 = z1, self._zero(z1)
         kl = torch.empty_like(eps)
         h_out = torch.empty(B, n_h + n_z, H, W, dtype=torch.float32, device=h.device)
         _capi.check(_capi.lib().iaf_chain_tail(_ptr(h), _ptr(logq0), _ptr(s1), _ptr(s2), _ptr(z2), _ptr(kl), _ptr(h_out), B, n_h, n_z,
@@ -236,13 +252,25 @@ class CVAELayerIAF(object):
         _capi.check(_capi.lib().iaf_chain_backward_pre(_ptr(down), _ptr(z2), _ptr(d_h), _ptr(gate), gscale, _ptr(dko), _ptr(dz2), _ptr(G),
                                                        _ptr(d_dc1), B, n_h, n_z, H * W, _stream()))
         ctx = st["context_sum"]
-        dz1, dctx2, grads2 = self.stack2.iaf_step_backward(st["z1"], ctx, z2, st["s2"], dz2, G, self._rel2)
+        if self.stack2 is not None:
+            dz1, dctx2, grads2 = self.stack2.iaf_step_backward(st["z1"], ctx, z2, st["s2"], dz2, G, self._rel2)
+        else:       # 'down_iaf2_deep': one flow; the second context gradient of iaf_chain_backward_post is zeros
+            dz1, dctx2, grads2 = dz2, self._zero(ctx), None
         dz0, dctx1, grads1 = self.stack.iaf_step_backward(st["z0"], ctx, st["z1"], st["s1"], dz1, G, self._rel)
         _capi.check(_capi.lib().iaf_chain_backward_post(_ptr(up), _ptr(down), _ptr(st["z0"]), _ptr(dz0), _ptr(G), _ptr(dctx1), _ptr(dctx2),
                                                         _ptr(d_up), _ptr(d_uc1), _ptr(d_dc1), B, n_h, n_z, H * W, _stream()))
+        if grads2 is None:
+            return dict(d_up_conv1=d_uc1, d_down_conv1=d_dc1, grads={self.name + "_deepiaf_" + k: v for k, v in grads1.items()})
         grads = {self.name + "_posterior_conv1_" + k: v for k, v in grads1.items()}
         grads.update({self.name + "_posterior_conv2_" + k: v for k, v in grads2.items()})
         return dict(d_up_conv1=d_uc1, d_down_conv1=d_dc1, grads=grads)
+
+    def _zero(self, like):
+        """a cached tensor of zeros with the shape of `like` (made on first use: warm up before a capture)"""
+        key = (tuple(like.shape), like.device)
+        if key not in self._zeros:
+            self._zeros[key] = torch.zeros_like(like)
+        return self._zeros[key]
 
     def _down_q_made(self, h, eps):
         """prior 'made' (models.py:272-291, 304-309, 317-318): iaf_made_head, the posterior's one or two steps, the prior's step on
@@ -364,7 +392,7 @@ class CVAELayerIAF(object):
             raise RuntimeError("backward() follows up() and down_q() in training mode")
         if self.prior == "made":
             return self._backward_made(d_h, d_obj, d_up)
-        if self.posterior == "down_iaf2_nl2":
+        if self.posterior in ("down_iaf2_nl2", "down_iaf2_deep"):
             return self._backward_chain(d_h, d_obj, d_up)
         n_h, n_z, st = self.n_h, self.n_z, self._st
         z = st["z"]

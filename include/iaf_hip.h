@@ -69,6 +69,37 @@ typedef struct iaf_stack iaf_stack_t;
 int iaf_stack_create(iaf_stack_t** out, int n_z, int n_h, int depth_ar, int variant);
 int iaf_stack_destroy(iaf_stack_t* s);
 
+/* The masked ResNet inside the IAF step -- N.ar.resnet (graphy/nodes/ar.py:428-448, 478-528), the autoregressive network of the
+ * posterior 'down_iaf2_deep' (models.py:104-108, 272-285) -- as a stack object.  With nl = elu and D = depth:
+ *     h_0     = conv_input(z) + context                  n_z -> n_h, NO nonlinearity (ar.py:502-504)
+ *     t_i     = elu(conv1_i(elu(h_i)))                   n_h -> n_h
+ *     h_{i+1} = h_i + 0.1 * conv2_i(t_i)                 n_h -> n_h      i = 0 .. D-1 (ar.py:437-441)
+ *     m_raw, s_raw = out_0(h_D), out_1(h_D)              n_h -> n_z, zero-diagonal, on the RAW stream (ar.py:511-514)
+ * Layers (iaf_layer_work, iaf_stack_get_precision, iaf_stack_set_tuning[_bf3]): 0 = the input conv, 2i+1 / 2i+2 = conv1 / conv2 of
+ * block i, 2 depth + 1 = the output pair.  The V / g / b (w / s / b) pointer order of iaf_stack_prepare, iaf_prep_batch_run,
+ * iaf_step_backward and iaf_wn_bwd_batch_run is the same: input, 0_conv1, 0_conv2, 1_conv1, ..., out_0, out_1 -- 2 depth + 3 convs,
+ * the reference's <name>_deepiaf_input, _deepiaf_<i>_conv1, _deepiaf_<i>_conv2, _deepiaf_out_0, _deepiaf_out_1.
+ * 1 <= depth <= 4, else IAF_ERR_SHAPE.  variant must be IAF_VARIANT_THEANO (resnet_layer_a passes no flipmask to its convs,
+ * ar.py:434-435, so only the plain ordering exists); n_z and n_h multiples of 16, at most 256; else IAF_ERR_UNSUPPORTED.
+ * n_z | n_h or n_h | n_z, else IAF_ERR_NOT_MULTIPLE.
+ * The step runs layer by layer on the conv kernels (2 depth + 2 launches), on the split products by default and on the exact
+ * fp32 MFMA under IAF_PRECISION_F32 and for c_in = 16.  Every stack entry point serves such a stack -- prepare and the prep batch,
+ * the workspace sizes, iaf_ar_multiconv2d_forward, iaf_step_forward, iaf_step_inverse[_device], iaf_stack_set_training,
+ * iaf_step_forward_train, iaf_step_backward, the deferred weight-norm batch, the work counts, iaf_stack_set_precision (F32 and
+ * the default) -- except these, which answer IAF_ERR_UNSUPPORTED:
+ *   iaf_posterior_block_forward / _forward_train / _backward   the block's kernels stage the posterior sample into the FIRST conv;
+ *                                                              'down_iaf2_deep' runs through iaf_chain_head / _tail instead
+ *   iaf_stack_autotune, iaf_step_time_layer                    they time the plain stack's launch sequence
+ *   iaf_stack_set_fuse_first / _set_fuse_step / _set_halo_exchange[_debug] / _set_packs
+ *                                                              there is no one-launch form of this step to steer, and both pack
+ *                                                              families stay in use (c_in = 16 has no split pack)
+ *   iaf_stack_set_precision(IAF_PRECISION_F16X2)               no kernel of this launch sequence reads fp16 planes (F32 and BF16X3 work)
+ * (the kind of stack is tested first: an unprepared resnet stack gets this answer too, not IAF_ERR_NOT_PREPARED)
+ * and iaf_stack_step_is_fused / _step_is_f16 / _step_exchanges / _step_pairs, which return 0.
+ * Backward: the 0.1 of `h_i + 0.1 conv2` reaches conv2's weight and bias gradients as a second, scaled output of the data-gradient
+ * epilogue that produces d h_{i+1} (it writes d h and 0.1 d h): no scale argument in the weight-gradient kernels, no extra launch. */
+int iaf_stack_create_resnet(iaf_stack_t** out, int n_z, int n_h, int depth, int variant);
+
 /* Replaces get_conv_ar_mask + the weight-norm lines of conv2d (layers.py:134-141, 56-60):
  *   v = mask*V ; w = exp(g)[o] * v / sqrt(max(sum_{h,w,i} v^2, 1e-12))
  * and repacks w into MFMA fragment order (dead taps dropped).  V/g/b: arrays of depth_ar+2
@@ -461,6 +492,10 @@ int iaf_stack_range_errors(const iaf_stack_t* s, unsigned* errors);
 /* 1 if the one-launch step of the stack at this size would run a two-plane fp16 kernel now, else 0 */
 int iaf_stack_step_is_f16(const iaf_stack_t* s, int B, int H, int W);
 int iaf_stack_get_precision(const iaf_stack_t* s, int layer, int B, int H, int W);
+/* The same for the DATA GRADIENT of layer `layer` in iaf_step_backward (dX = W^T dY on the transposed pack): IAF_PRECISION_BF16X3 where the
+ * launch at this size runs the split products, else IAF_PRECISION_F32.  IAF_ERR_NOT_PREPARED unless iaf_stack_set_training is on (the
+ * transposed problems exist only then) and for a generic stack.  Same decision function as the launch; no device work. */
+int iaf_stack_get_dgrad_precision(const iaf_stack_t* s, int layer, int B, int H, int W);
 /* launch shape of the bf16x3 kernel for GEMM layer `layer`: co tiles per wave, pixel tiles per wave, waves along
  * pixels, K-slice waves, co groups sharing one staged activation tile (nt = 0 restores the automatic choice) */
 int iaf_stack_set_tuning_bf3(iaf_stack_t* s, int layer, int nt, int ppw, int pxt, int ks, int wco);
