@@ -18,6 +18,11 @@ struct iaf_conv3x3 : PackState {   // precision, packs (iaf_conv3x3_set_packs), 
     PrepLayer* d_desc = nullptr;
     bool training = false;
     bool deconv = false;           // weights prepared by iaf_conv3x3_prepare_deconv (deconv2d's norm + rotated filter)
+    // the plain conv of the Theano statement (iaf_conv3x3_create_theano; graphy/nodes/conv.py:122-260): weights w OIHW [n_out][n_in+1][3][3],
+    // s, b; the pack is flipped at prep time (prep_tile_plain_theano), so launches keep the TF tap tables and `variant` stays
+    // IAF_VARIANT_TF; L.bias is the position-class table [16][ncot*16], L.border the eight border weights [8][ncot*16]
+    bool theano_plain = false;
+    bool dgrad_pinned = false;     // iaf_conv3x3_set_dgrad_tuning: the data gradient runs the split products in the shape T.b_* at every size
     // forward on the bf16 matrix cores (bf16x3 split products, iaf_conv_bf3.hpp with 9 taps): plain convs with c_in % 32 == 0
     // IAF_PRECISION_F16X2 (round 6): as BF16X3, the stride-1 forward launches on TWO fp16 planes (iaf_conv_bf3.hpp F16) from the pack L.wp2;
     // an operand beyond 65504 raises rng_err (mapped host memory): the next forward returns IAF_ERR_RANGE once and the conv runs bf16x3
@@ -53,7 +58,7 @@ static inline bool conv_f16_active(const iaf_conv3x3* c) {
 static inline void conv_prep_packs(const iaf_conv3x3* c, PrepLayer& P) {
     prep_layer_packs(P, c->L, pack_prep_writes(*c, PACK_CONV, conv_f16_active(c), c->L.wp3 != nullptr, c->training), c->rng.dev);
 }
-static int conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out, int mask_mode);
+static int conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out, int mask_mode, bool theano_plain = false);
 extern "C" int iaf_conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out) { return conv3x3_create(out, n_in, n_out, 0); }
 extern "C" int iaf_conv3x3_create_masked(iaf_conv3x3_t** out, int n_in, int n_out, int zerodiagonal) {
     if (n_in > 0 && n_out > 0 && !(n_in % n_out == 0 || n_out % n_in == 0)) return IAF_ERR_NOT_MULTIPLE;   // layers.py:116
@@ -73,13 +78,22 @@ extern "C" int iaf_conv3x3_create_masked_theano(iaf_conv3x3_t** out, int n_in, i
     return IAF_OK;
 }
 
-static int conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out, int mask_mode) {
+// N.conv.conv2d(name, n_in, n_out, (3,3), w=w) of the Theano path (graphy/nodes/conv.py:122-260; up_conv1/2, down_conv1/2 of
+// models.cvae_layer, models.py:59-108): include/iaf_hip.h has the contract
+extern "C" int iaf_conv3x3_create_theano(iaf_conv3x3_t** out, int n_in, int n_out) {
+    if (!out) return IAF_ERR_NULL;
+    *out = nullptr;
+    if (n_in > 0 && n_out > 0 && (n_in % 16 != 0 || n_out % 16 != 0 || n_in > 16 * PREP_MAXI)) return IAF_ERR_UNSUPPORTED;    // (no generic form)
+    return conv3x3_create(out, n_in, n_out, 0, true);
+}
+
+static int conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out, int mask_mode, bool theano_plain) {
     if (!out) return IAF_ERR_NULL;
     *out = nullptr;
     if (n_in <= 0 || n_out <= 0) return IAF_ERR_SHAPE;
     iaf_conv3x3* c = new (std::nothrow) iaf_conv3x3();
     if (!c) return (int)hipErrorOutOfMemory;
-    c->n_in = n_in; c->n_out = n_out; c->prepared = false; c->mask_mode = mask_mode;
+    c->n_in = n_in; c->n_out = n_out; c->prepared = false; c->mask_mode = mask_mode; c->theano_plain = theano_plain;
     c->generic = (n_in % 16 != 0 || n_out % 16 != 0 || n_in > 16 * PREP_MAXI);
     GemmLayer& L = c->L;
     L.cin = n_in; L.cout = n_out; L.npair = 1; L.zerodiag = (mask_mode == 2) ? 1 : 0; L.full3x3 = (mask_mode == 0);
@@ -89,7 +103,8 @@ static int conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out, int mask_mod
     if (mask_mode) count_macs(L, n_in, n_out, L.zerodiag, 1);
     int rc;
     if ((rc = (int)hipMalloc(&L.wp, c->generic ? (size_t)MAXTAPS * n_in * n_out * sizeof(float) : pack_bytes_f32(L, MAXTAPS))) != 0 ||
-        (rc = (int)hipMalloc(&L.bias, ((size_t)L.ncot * 16 + (size_t)n_in) * sizeof(float))) != 0 ||   // + deconv norms
+        (rc = (int)hipMalloc(&L.bias, ((size_t)L.ncot * 16 * (theano_plain ? 16 : 1) + (size_t)n_in) * sizeof(float))) != 0 ||   // + deconv norms
+        (theano_plain && (rc = (int)hipMalloc(&L.border, (size_t)(MAXTAPS - 1) * L.ncot * 16 * sizeof(float))) != 0) ||
         (rc = (int)hipHostMalloc((void**)&c->h_desc, sizeof(PrepLayer))) != 0 ||
         (rc = (int)hipMalloc((void**)&c->d_desc, sizeof(PrepLayer))) != 0) {
         iaf_conv3x3_destroy(c);
@@ -100,7 +115,7 @@ static int conv3x3_create(iaf_conv3x3_t** out, int n_in, int n_out, int mask_mod
         return rc;
     }
     // default arithmetic of a plain conv with a split pack: the two-plane fp16 forward (IAF_DEFAULT_PRECISION=bf16x3: round 5's)
-    if (L.wp3) {
+    if (L.wp3 && !theano_plain) {     // (the Theano plain conv has no fp16-plane form: bf16x3, the PackState default)
         static const bool f16_default = !(getenv("IAF_DEFAULT_PRECISION") && !strcmp(getenv("IAF_DEFAULT_PRECISION"), "bf16x3"));
         if (f16_default) {
             rc = iaf_conv3x3_set_precision(c, IAF_PRECISION_F16X2);
@@ -135,7 +150,7 @@ extern "C" int iaf_conv3x3_prepare(iaf_conv3x3_t* c, const float* V, const float
     } else {
         PrepLayer& P = *c->h_desc;
         memset(&P, 0, sizeof(P));
-        P.V[0] = V; P.g[0] = g; P.b[0] = b; P.variant = PREP_PLAIN9;
+        P.V[0] = V; P.g[0] = g; P.b[0] = b; P.variant = c->theano_plain ? PREP_PLAIN9_THEANO : PREP_PLAIN9;
         conv_prep_packs(c, P);
         prep_layer_geometry(P, L, 0);
         HIP_TRY(hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(PrepLayer), hipMemcpyHostToDevice, (hipStream_t)stream));
@@ -156,6 +171,7 @@ extern "C" int iaf_conv3x3_prepare(iaf_conv3x3_t* c, const float* V, const float
 // The object is an ordinary iaf_conv3x3 (n_in, n_out) afterwards: run it with iaf_conv3x3_forward on the zero-inserted
 // input (iaf_resample2 mode IAF_RESAMPLE_UP_ZERO_ODD) at the OUTPUT resolution.  Forward only.
 extern "C" int iaf_conv3x3_prepare_deconv(iaf_conv3x3_t* c, const float* V, const float* g, const float* b, void* stream) {
+    if (c && c->theano_plain) return IAF_ERR_UNSUPPORTED;
     if (!c || !V || !g || !b) return IAF_ERR_NULL;
     if (c->mask_mode) return IAF_ERR_UNSUPPORTED;
     if (c->packs != IAF_PACK_ALL) return IAF_ERR_UNSUPPORTED;    // (the deconv packs derive from the fp32 one)
@@ -224,7 +240,7 @@ extern "C" int iaf_conv3x3_prep_batch_create(iaf_conv3x3_prep_batch_t** out, iaf
     if (int rc = b->t.create(tiles, false)) { iaf_conv3x3_prep_batch_destroy(b); return rc; }
     for (int i = 0; i < n; ++i) {
         PrepLayer& P = b->t.h[i];
-        P.variant = PREP_PLAIN9;
+        P.variant = convs[i]->theano_plain ? PREP_PLAIN9_THEANO : PREP_PLAIN9;
         conv_prep_packs(convs[i], P);
         prep_layer_geometry(P, convs[i]->L, b->t.begin[i]);
     }
@@ -270,12 +286,13 @@ extern "C" int iaf_conv3x3_set_tuning(iaf_conv3x3_t* c, int nt, int pxt, int wco
     GemmLayer& L = c->L;
     if (nt == 0) { L.user_tuned = false; c->bf3_choice = 1; return IAF_OK; }     // back to the automatic choice
     if (nt < 0) {           // a bf16x3 launch shape, as iaf_conv3x3_autotune reports it: (-nt, ppw, wco, ks), pxt = 1
-        if (c->generic || c->mask_mode || !L.wp3 || !bf3_ragged_ok(L.ncot, -nt * wco) || !pick_bf3p(-nt, pxt, 1, ks, wco, BF3P_PLAIN)) return IAF_ERR_UNSUPPORTED;
+        if (c->generic || c->mask_mode || !L.wp3 || !bf3_ragged_ok(L.ncot, -nt * wco) ||
+            !pick_bf3p(-nt, pxt, 1, ks, wco, c->theano_plain ? BF3P_PLAIN_TH : BF3P_PLAIN)) return IAF_ERR_UNSUPPORTED;
         L.b_nt = -nt; L.b_ppw = pxt; L.b_pxt = 1; L.b_ks = ks; L.b_wco = wco;
         c->bf3_choice = 2;
         return IAF_OK;
     }
-    if (c->generic || !pick_kernel(nt, pxt, wco, ks, IN_NCHW, c->mask_mode ? EPI_PLAIN5 : EPI_PLAIN)) return IAF_ERR_UNSUPPORTED;
+    if (c->generic || !pick_kernel(nt, pxt, wco, ks, IN_NCHW, c->mask_mode ? EPI_PLAIN5 : c->theano_plain ? EPI_PLAIN_TH : EPI_PLAIN)) return IAF_ERR_UNSUPPORTED;
     if (L.ncot % (nt * wco) != 0 || L.nchunk < ks) return IAF_ERR_UNSUPPORTED;
     L.nt = nt; L.pxt = pxt; L.wco = wco; L.ks = ks; L.user_tuned = true;
     c->bf3_choice = 3;      // a pinned fp32 shape means the fp32 kernel
@@ -322,12 +339,13 @@ static int conv3x3_launch(GemmLayer& L, ConvP& p, int epi_sel, int inmode, bool 
                           int variant = IAF_VARIANT_TF, int bf3_choice = 3, unsigned* f16_rng = nullptr, bool dgrad16 = false) {
     // the plain conv on the bf16 matrix cores: forward (NCHW input, EPI_PLAIN), or its data gradient (L = the transposed
     // problem with wp3 = the transposed bf16x3 pack: dY pixel-major, mirrored taps, EPI_DGRAD)
-    const bool fwd3 = !masked && !mirror && epi_sel == EPI_PLAIN && inmode == IN_NCHW;
+    const bool th = epi_sel == EPI_PLAIN_TH;        // the Theano plain conv: the same launch, the forms with the position-class bias table
+    const bool fwd3 = !masked && !mirror && (epi_sel == EPI_PLAIN || th) && inmode == IN_NCHW;
     const bool bwd3 = !masked && mirror && epi_sel == EPI_DGRAD9 && inmode == IN_PIXMAJOR && variant == IAF_VARIANT_TF;
     const bool f16l = (fwd3 && f16_rng != nullptr) || (bwd3 && dgrad16 && L.wp2 != nullptr);
     if ((fwd3 || bwd3) && conv3x3_bf3_shape(L, bf3_choice, p.P, p.W, f16l) &&
-        pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, bwd3 ? BF3P_DGRAD : BF3P_PLAIN)) {
-        conv_fn_t fn = pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, bwd3 ? BF3P_DGRAD : BF3P_PLAIN);
+        pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, bwd3 ? BF3P_DGRAD : th ? BF3P_PLAIN_TH : BF3P_PLAIN)) {
+        conv_fn_t fn = pick_bf3p(L.b_nt, L.b_ppw, L.b_pxt, L.b_ks, L.b_wco, bwd3 ? BF3P_DGRAD : th ? BF3P_PLAIN_TH : BF3P_PLAIN);
         const int tm = 16 * L.b_ppw * L.b_pxt, W = p.W, sg = bwd3 ? -1 : 1;
         p.border = nullptr; p.wp = (const float*)L.wp3; p.bias = L.bias; p.lim = nullptr;
         // f16_rng (the caller's conv runs IAF_PRECISION_F16X2): the forward on two fp16 planes, the same launch shape and LDS bound
@@ -443,7 +461,7 @@ extern "C" int iaf_conv3x3_forward(iaf_conv3x3_t* c, const float* x, const float
         const int need = f16 ? IAF_PACK_F16X2 : split ? IAF_PACK_BF16X3 : IAF_PACK_F32;
         if (!(c->packs & need)) return IAF_ERR_NOT_PREPARED;
     }
-    return conv3x3_launch(L, p, c->mask_mode ? EPI_PLAIN5 : EPI_PLAIN, IN_NCHW, c->mask_mode != 0, false, st, c->variant,
+    return conv3x3_launch(L, p, c->mask_mode ? EPI_PLAIN5 : c->theano_plain ? EPI_PLAIN_TH : EPI_PLAIN, IN_NCHW, c->mask_mode != 0, false, st, c->variant,
                           (conv_split(c) && !c->deconv) ? c->bf3_choice : 3, conv_f16_active(c) ? c->rng.dev : nullptr);
 }
 
@@ -534,6 +552,7 @@ static int conv3x3_prior_launch(iaf_conv3x3_t* c, const float* x, int elu_input,
 
 extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, const float* eps, float* z,
                                                 float* h_det, int B, int H, int W, void* stream) {
+    if (c && c->theano_plain) return IAF_ERR_UNSUPPORTED;
     if (!c || !x || !eps || !z || !h_det) return IAF_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || n_z <= 0 || n_h <= 0) return IAF_ERR_SHAPE;
     if ((long long)B * H * W > (1LL << 30) / 64) return IAF_ERR_SHAPE;
@@ -548,6 +567,7 @@ extern "C" int iaf_conv3x3_forward_prior_sample(iaf_conv3x3_t* c, const float* x
 // kernel of its own.  Arithmetic, range word, fallbacks: the prior form's.
 extern "C" int iaf_conv3x3_forward_hdet(iaf_conv3x3_t* c, const float* x, int elu_input, int n_z, int n_h, float* h_det, int B, int H, int W,
                                         void* stream) {
+    if (c && c->theano_plain) return IAF_ERR_UNSUPPORTED;
     if (!c || !x || !h_det) return IAF_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || n_z <= 0 || n_h <= 0) return IAF_ERR_SHAPE;
     if ((long long)B * H * W > (1LL << 30) / 64) return IAF_ERR_SHAPE;
@@ -590,6 +610,7 @@ static conv_fn_t s2_shape(const GemmLayer& L, int s2, int W, int* sh, size_t* ld
 // (then: iaf_conv3x3_forward at [2H,2W] + iaf_resample2 DOWN_ODD, the same numbers).
 extern "C" int iaf_conv3x3_forward_stride2(iaf_conv3x3_t* c, const float* x, int elu_input, float* const* outs, const int* out_channels,
                                            int n_outs, int B, int H, int W, void* stream) {
+    if (c && c->theano_plain) return IAF_ERR_UNSUPPORTED;
     if (!c || !x || !outs || !out_channels) return IAF_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || n_outs < 1 || n_outs > MAXSPLIT) return IAF_ERR_SHAPE;
     if ((long long)B * H * W > (1LL << 30) / 64) return IAF_ERR_SHAPE;
@@ -646,6 +667,7 @@ extern "C" int iaf_conv3x3_forward_stride2(iaf_conv3x3_t* c, const float* x, int
 // instead of 36.  IAF_ERR_UNSUPPORTED: run iaf_conv3x3_forward on the zero-inserted inputs (same numbers up to fp32 rounding).
 extern "C" int iaf_conv3x3_forward_deconv(iaf_conv3x3_t* c, const float* x, const float* x2, int c_split, int elu_input,
                                           const float* residual, float* out, int B, int H, int W, void* stream) {
+    if (c && c->theano_plain) return IAF_ERR_UNSUPPORTED;
     if (!c || !x || !out) return IAF_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0) return IAF_ERR_SHAPE;
     if ((long long)B * H * W > (1LL << 30) / 256) return IAF_ERR_SHAPE;
@@ -685,6 +707,7 @@ extern "C" int iaf_conv3x3_forward_deconv(iaf_conv3x3_t* c, const float* x, cons
 // which packs the prep launches of a plain conv keep up to date (as iaf_stack_set_packs): a conv that runs at ONE size needs one
 extern "C" int iaf_conv3x3_set_packs(iaf_conv3x3_t* c, int packs) {
     if (!c) return IAF_ERR_NULL;
+    if (c->theano_plain && packs == IAF_PACK_F16X2) return IAF_ERR_UNSUPPORTED;
     PackFacts f;
     f.generic = c->generic; f.masked = c->mask_mode != 0; f.training = c->training; f.deconv = c->deconv;
     f.all_split = c->L.wp3 != nullptr; f.f16_active = conv_f16_active(c);
@@ -692,11 +715,12 @@ extern "C" int iaf_conv3x3_set_packs(iaf_conv3x3_t* c, int packs) {
 }
 extern "C" int iaf_conv3x3_set_precision(iaf_conv3x3_t* c, int precision) {
     if (!c) return IAF_ERR_NULL;
+    if (c->theano_plain && precision == IAF_PRECISION_F16X2) return IAF_ERR_UNSUPPORTED;
     if (precision != IAF_PRECISION_F32 && precision != IAF_PRECISION_BF16X3 && precision != IAF_PRECISION_F16X2) return IAF_ERR_SHAPE;
     bool new_pack = false;
     if (precision == IAF_PRECISION_F16X2) {
         GemmLayer& L = c->L;
-        if (c->generic || c->mask_mode || !L.wp3) return IAF_ERR_UNSUPPORTED;       // (plain convs with c_in % 32 == 0: the same fragments, two planes)
+        if (c->generic || c->mask_mode || !L.wp3 || c->theano_plain) return IAF_ERR_UNSUPPORTED;       // (plain convs with c_in % 32 == 0: the same fragments, two planes)
         if (int rc = c->rng.alloc()) return rc;
         if (!L.wp2) {
             HIP_TRY(hipMalloc(&L.wp2, pack_bytes_split(L, MAXTAPS, 2)));
@@ -727,6 +751,7 @@ extern "C" int iaf_conv3x3_autotune(iaf_conv3x3_t* c, const float* x, const floa
                                     const float* residual, float* const* outs, const int* out_channels, int n_outs, int B,
                                     int H, int W, int reps, void* stream, int* best_shape, float* best_us) {
     if (!c) return IAF_ERR_NULL;
+    if (c->theano_plain) return IAF_ERR_UNSUPPORTED;
     if (c->generic) return IAF_OK;
     if (reps <= 0) reps = 20;
     hipStream_t st = (hipStream_t)stream;
@@ -837,12 +862,20 @@ extern "C" int iaf_conv3x3_set_training(iaf_conv3x3_t* c, int on) {
     // fp16 planes: the data gradient of a conv whose arithmetic is IAF_PRECISION_F16X2 (iaf_conv_bf3.hpp DG16; IAF_DGRAD_F16=0: dev knob)
     static const bool dg16_env = !(getenv("IAF_DGRAD_F16") && getenv("IAF_DGRAD_F16")[0] == '0');
     if (int rc = gemm_layer_set_training(L, c->T, MAXTAPS, dg16_env)) return rc;
-    c->training = true;
+    c->training = true; c->dgrad_pinned = false;
     pack_set_training(*c);    // (training keeps every pack)
     return IAF_OK;
 }
 
-struct ConvTrainWs { float* xe; float* dyc; float* part; float* dW; float* dbp; unsigned short* tapmask; };
+#define CONV_BRD_SLABS 64      // pixel slabs of the Theano plain conv's border-tap sums (iaf_border9_sum_kernel)
+// which family the data gradient runs (conv3x3_bf3_shape's `choice`): bf16x3 unless the conv's precision is fp32 or a backward search
+// measured the fp32 kernel faster at this size; 2 = the pinned shape (iaf_conv3x3_set_dgrad_tuning)
+static int conv3x3_dgrad_choice(const iaf_conv3x3* c, long long P, int W) {
+    if (!conv_split(c) || c->bf3_choice == 3 || !c->T.wp3) return 3;
+    if (c->dgrad_pinned) return 2;
+    return (c->T.tuned_P == P && c->T.tuned_W == W && !c->T.tuned_bf3) ? 3 : 1;
+}
+struct ConvTrainWs { float* xe; float* dyc; float* part; float* dW; float* dbp; unsigned short* tapmask; float* dbrd; };
 static size_t conv3x3_train_ws_floats(const iaf_conv3x3* c, long long P, ConvTrainWs* o, float* base) {
     size_t off = 0;
     auto take = [&](size_t n) { float* q = base ? base + off : nullptr; off += (n + 63) / 64 * 64; return q; };
@@ -853,6 +886,7 @@ static size_t conv3x3_train_ws_floats(const iaf_conv3x3* c, long long P, ConvTra
     t.dW = take((size_t)MAXTAPS * c->n_in * c->n_out);
     t.dbp = take((size_t)256 * c->n_out);
     t.tapmask = (unsigned short*)take(((size_t)P + 1) / 2);
+    t.dbrd = c->theano_plain ? take((size_t)CONV_BRD_SLABS * (MAXTAPS - 1) * c->n_out) : nullptr;
     if (o) *o = t;
     return off;
 }
@@ -961,7 +995,7 @@ extern "C" int iaf_conv3x3_backward(iaf_conv3x3_t* c, const float* x, const floa
             p.split_ptr[k] = dxs[k < n_dxs ? k : n_dxs - 1];
         }
         // bf16x3 unless the conv's precision is fp32 or a backward search measured the fp32 kernel faster at this size
-        const int choice3 = (!conv_split(c) || c->bf3_choice == 3 || !c->T.wp3) ? 3 : (c->T.tuned_P == (long long)P && c->T.tuned_W == W && !c->T.tuned_bf3) ? 3 : 1;
+        const int choice3 = conv3x3_dgrad_choice(c, P, W);
         const bool dgrad16 = pack_f16_wanted(*c) && c->T.wp2 != nullptr && !c->deconv;
         if ((rc = conv3x3_launch(c->T, p, EPI_DGRAD9, IN_PIXMAJOR, false, true, st, IAF_VARIANT_TF, choice3, nullptr, dgrad16))) return rc;
     }
@@ -999,8 +1033,40 @@ extern "C" int iaf_conv3x3_backward(iaf_conv3x3_t* c, const float* x, const floa
     memset(&w, 0, sizeof(w));
     w.V = V; w.g = g; w.dW = dWbuf; w.dbp = dbpbuf; w.dV = dV; w.dg = dg; w.db = db;
     w.cin = L.cin; w.cout = L.cout; w.cout_packed = L.cout; w.nslab = nslab; w.pack_stride = 1;
+    if (c->theano_plain) {
+        // the border channel's eight taps: sums of dY over the pixels whose tap leaves the image, from the tap table (the `dbrd` of the
+        // stack's Theano backward, eight taps), then the Theano statement's norm (all n_in + 1 channels, exp(3 s), OIHW)
+        const int nb = P < CONV_BRD_SLABS * 64 ? (P + 63) / 64 : CONV_BRD_SLABS;
+        const int per = (P + nb - 1) / nb;
+        hipLaunchKernelGGL(iaf_border9_sum_kernel, dim3((L.cout + 63) / 64, nb), dim3(256), 0, st, (const float*)tw.dyc, tapmask, tw.dbrd, P, L.cout, per);
+        w.dbrd = tw.dbrd; w.nbrd = nb; w.variant = PREP_PLAIN9_THEANO;
+        hipLaunchKernelGGL(iaf_wn_bwd_plain_theano_kernel, dim3(L.cout / 16), dim3(256), 0, st, w);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(iaf_wn_bwd_plain_kernel, dim3(L.cout / 16), dim3(256), 0, st, w);
     return (int)hipGetLastError();
+}
+
+// 1 if the data gradient of a backward call at this size would run the split products (bf16x3, or two fp16 planes where the conv's
+// precision asks for them)
+extern "C" int iaf_conv3x3_dgrad_runs_bf16x3(iaf_conv3x3_t* c, int B, int H, int W) {
+    if (!c || c->generic || !c->training || B <= 0 || H <= 0 || W <= 0) return 0;
+    const long long P = (long long)B * H * W;
+    GemmLayer t = c->T;
+    const bool dgrad16 = pack_f16_wanted(*c) && c->T.wp2 != nullptr && !c->deconv;
+    return conv3x3_bf3_shape(t, conv3x3_dgrad_choice(c, P, W), P, W, dgrad16) && pick_bf3p(t.b_nt, t.b_ppw, t.b_pxt, t.b_ks, t.b_wco, BF3P_DGRAD) ? 1 : 0;
+}
+// pin the data gradient's split-product launch shape (nt, ppw, wco, ks; pxt = 1), as iaf_conv3x3_set_tuning(-nt, ...) pins the forward's;
+// nt = 0: back to the size rule.  After iaf_conv3x3_set_training (which rebuilds the transposed problem).
+extern "C" int iaf_conv3x3_set_dgrad_tuning(iaf_conv3x3_t* c, int nt, int ppw, int wco, int ks) {
+    if (!c) return IAF_ERR_NULL;
+    if (nt == 0) { c->dgrad_pinned = false; return IAF_OK; }
+    if (!c->training) return IAF_ERR_NOT_PREPARED;
+    GemmLayer& T = c->T;
+    if (c->generic || nt < 0 || !T.wp3 || !bf3_ragged_ok(T.ncot, nt * wco) || !pick_bf3p(nt, ppw, 1, ks, wco, BF3P_DGRAD)) return IAF_ERR_UNSUPPORTED;
+    T.b_nt = nt; T.b_ppw = ppw; T.b_pxt = 1; T.b_ks = ks; T.b_wco = wco;
+    c->dgrad_pinned = true;
+    return IAF_OK;
 }
 
 // Launch-shape search for the data gradient (the transposed problem has its own best shape): times whole
@@ -1012,6 +1078,7 @@ extern "C" int iaf_conv3x3_autotune_backward(iaf_conv3x3_t* c, const float* x, c
                                              int W, void* workspace, size_t workspace_bytes, int reps, void* stream,
                                              int* best_shape, float* best_us) {
     if (!c) return IAF_ERR_NULL;
+    if (c->theano_plain) return IAF_ERR_UNSUPPORTED;
     if (!c->training) return IAF_ERR_NOT_PREPARED;
     if (reps <= 0) reps = 10;
     hipStream_t st = (hipStream_t)stream;
@@ -1087,6 +1154,7 @@ extern "C" int iaf_conv3x3_autotune_backward(iaf_conv3x3_t* c, const float* x, c
 // ---- deferred weight-norm backward of many plain convs in one launch ----------------------------------------------
 extern "C" int iaf_conv3x3_set_defer_weightnorm(iaf_conv3x3_t* c, int on) {
     if (!c) return IAF_ERR_NULL;
+    if (on && c->theano_plain) return IAF_ERR_UNSUPPORTED;
     if (on && !c->training) return IAF_ERR_NOT_PREPARED;
     if (on) {
         if (!c->own_dW) HIP_TRY(hipMalloc(&c->own_dW, (size_t)MAXTAPS * c->n_in * c->n_out * sizeof(float)));
@@ -1113,6 +1181,8 @@ extern "C" int iaf_conv3x3_wn_bwd_batch_create(iaf_conv3x3_wn_bwd_batch_t** out,
     if (!out || !convs) return IAF_ERR_NULL;
     *out = nullptr;
     if (n <= 0) return IAF_ERR_SHAPE;
+    for (int i = 0; i < n; ++i)
+        if (convs[i] && convs[i]->theano_plain) return IAF_ERR_UNSUPPORTED;
     std::vector<int> tiles;
     if (int rc = conv_batch_tiles(convs, n, &tiles)) return rc;
     iaf_conv3x3_wn_bwd_batch* b = new (std::nothrow) iaf_conv3x3_wn_bwd_batch();

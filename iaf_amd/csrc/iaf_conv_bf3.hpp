@@ -100,7 +100,8 @@ __device__ __forceinline__ void f16s_store4(char* smem, int slot, int q, f32x4 v
 // F16 = 1 (round 6): the operands as TWO fp16 planes and three part-products per step ("f16x2", see f16s_split2 above and
 // iaf_step_fused.hpp) -- the forward plain convs (EPI_PLAIN, NCHW input: activations O(1), weight-normed filters); the data gradients keep
 // the bf16 planes (a gradient tensor's magnitudes have no business with fp16's exponent range).  p.wp = the two-plane pack.
-template <int NT, int PPW, int PXT, int KS, int INMODE, int EPI, int WCO = 1, int NTP_ = NTAPS, int S2 = 0, int F16 = 0>
+// BCLS: EPI_PLAIN with the position-class bias table of the Theano plain conv (iaf_conv_epilogue.hpp, epi_load); its own compile-time form
+template <int NT, int PPW, int PXT, int KS, int INMODE, int EPI, int WCO = 1, int NTP_ = NTAPS, int S2 = 0, int F16 = 0, int BCLS = 0>
 __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP p) {
     static_assert(!F16 || INMODE != IN_FUSED0, "the fused first layer exists on bf16 planes only");
     // F16 with a pixel-major input = the DATA GRADIENT on two fp16 planes (round 6): a gradient tensor has no business with fp16's exponent
@@ -749,7 +750,7 @@ __global__ __launch_bounds__(64 * PXT * KS * WCO) void iaf_conv_bf3_kernel(ConvP
         const int q = item / NUNIT, u = item - q * NUNIT;
         g[i] = epi_geom(p, P0 + (pw * PPW + q) * 16 + pl, kk, item < NITEM && cot0 + u * TPU < (EPI == EPI_PRIOR ? p.pr_nlt : p.ncot));
         if constexpr (S2 == 2) g[i].up = 4 + 2 * ph_a + ph_b;
-        epi_load<EPI>(p, g[i], cot0 + u * TPU, ops[i]);
+        epi_load<EPI, BCLS>(p, g[i], cot0 + u * TPU, ops[i]);
     }
     f32x4 val[NMY][TPU];
     if constexpr (KS > 1) {

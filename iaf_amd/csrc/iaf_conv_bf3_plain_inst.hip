@@ -16,14 +16,14 @@
 
 // NT = 2, 4, 5.  (WCO = 3: 768 threads, three waves per SIMD, 170 registers -- NT = 5 does not fit and is not instantiated;
 // the prior form works in two-tile units: NT = 2, 4)
-template <int INMODE, int EPI, int S2 = 0, int F16 = 0>
+template <int INMODE, int EPI, int S2 = 0, int F16 = 0, int BCLS = 0>
 static conv_fn_t pick_nt(int nt) {
     switch (nt) {
-        case 2: return iaf_conv_bf3_kernel<2, IAF_PPW, IAF_PXT, IAF_KS, INMODE, EPI, IAF_WCO, MAXTAPS, S2, F16>;
-        case 4: return iaf_conv_bf3_kernel<4, IAF_PPW, IAF_PXT, IAF_KS, INMODE, EPI, IAF_WCO, MAXTAPS, S2, F16>;
+        case 2: return iaf_conv_bf3_kernel<2, IAF_PPW, IAF_PXT, IAF_KS, INMODE, EPI, IAF_WCO, MAXTAPS, S2, F16, BCLS>;
+        case 4: return iaf_conv_bf3_kernel<4, IAF_PPW, IAF_PXT, IAF_KS, INMODE, EPI, IAF_WCO, MAXTAPS, S2, F16, BCLS>;
     }
     if constexpr (IAF_WCO < 3 && EPI != EPI_PRIOR)
-        if (nt == 5) return iaf_conv_bf3_kernel<5, IAF_PPW, IAF_PXT, IAF_KS, INMODE, EPI, IAF_WCO, MAXTAPS, S2, F16>;
+        if (nt == 5) return iaf_conv_bf3_kernel<5, IAF_PPW, IAF_PXT, IAF_KS, INMODE, EPI, IAF_WCO, MAXTAPS, S2, F16, BCLS>;
     return nullptr;
 }
 
@@ -32,6 +32,9 @@ extern "C" conv_fn_t IAF_CAT(iaf_pick_bf3p_, IAF_PPW, IAF_PXT, IAF_KS, IAF_WCO)(
         // the data gradient of the conv: dY pixel-major, transposed bf16x3 pack, mirrored taps (iaf_conv3x3_backward)
         case BF3P_DGRAD: return pick_nt<IN_PIXMAJOR, EPI_DGRAD>(nt);
         case BF3P_PLAIN: return pick_nt<IN_NCHW, EPI_PLAIN>(nt);
+        // the plain conv of the Theano statement (graphy/nodes/conv.py:122-260): the same K loop on the flipped pack, bias from the
+        // position-class table
+        case BF3P_PLAIN_TH: return pick_nt<IN_NCHW, EPI_PLAIN, 0, 0, 1>(nt);
 #if IAF_S2
         // the downsampling layer's strided convs at their minimal work (iaf_conv_bf3.hpp, S2): conv2d stride 2, deconv2d by phases
         case BF3P_S2: return pick_nt<IN_NCHW, EPI_PLAIN, 1>(nt);

@@ -59,11 +59,18 @@ __device__ __forceinline__ int prior_pack_tile(const ConvP& p, int lt) {
 }
 
 // operands of the epilogue that do not depend on the GEMM (issued before the split-K exchange so their latency hides)
-template <int EPI>
+// BCLS (EPI_PLAIN only): the plain conv of the Theano statement -- p.bias is the position-class table [16][ncot * 16] (iaf_conv_kernel.hpp)
+template <int EPI, int BCLS = 0>
 __device__ __forceinline__ void epi_load(const ConvP& p, const EpiGeom& g, int cot, EpiOps& o) {
     if (!g.pvalid) return;
     const int HW = p.HW;
     if (EPI == EPI_PLAIN) {         // plain conv2d (layers.py:63-64): bias, and the residual of `input + 0.1 * h` (tf_train.py:44,94)
+        if constexpr (BCLS) {
+            int h, w;
+            fast_divmod(g.pp, p.W, 1.0f / (float)p.W, h, w);
+            const int cls = (h == 0 ? 1 : 0) | (h == p.H - 1 ? 2 : 0) | (w == 0 ? 4 : 0) | (w == p.W - 1 ? 8 : 0);
+            o.b0 = *(const f32x4*)(p.bias + ((size_t)cls * p.ncot + cot) * 16 + 4 * g.kk);
+        } else
         o.b0 = *(const f32x4*)(p.bias + cot * 16 + 4 * g.kk);
         if (p.res) {
             const size_t cb = ((size_t)g.bimg * p.cout + cot * 16 + 4 * g.kk) * HW + g.pp;

@@ -16,6 +16,10 @@ static conv_fn_t pick_mode(int inmode, int epi) {
         if (inmode == IN_NCHW) return iaf_conv_kernel<NT, IAF_PXT, IAF_WCO, IAF_KS, IN_NCHW, EPI_PLAIN, MAXTAPS>;
         return nullptr;
     }
+    if (epi == EPI_PLAIN_TH) {   // ... in the Theano statement (conv.py:122-260): the bias comes from the position-class table
+        if (inmode == IN_NCHW) return iaf_conv_kernel<NT, IAF_PXT, IAF_WCO, IAF_KS, IN_NCHW, EPI_PLAIN, MAXTAPS, false, 1>;
+        return nullptr;
+    }
     if (epi == EPI_DGRAD9) {  // data gradient of a plain 9-tap conv: pixel-major dY in, NCHW (split) out
         if (inmode == IN_PIXMAJOR) return iaf_conv_kernel<NT, IAF_PXT, IAF_WCO, IAF_KS, IN_PIXMAJOR, EPI_DGRAD, MAXTAPS>;
         return nullptr;

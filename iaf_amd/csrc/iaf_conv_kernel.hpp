@@ -36,6 +36,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 #define EPI_RES 8      // residual stream of the masked ResNet (graphy/nodes/ar.py:428-448, 478-528): v = acc + bias [+ ctx (+ ctx2)];
                        // skip != NULL: v = skip + 0.1 v;  y = v (raw, pixel-major);  y2 != NULL: y2 = elu(v) (pixel-major)
+#define EPI_PLAIN_TH 10  // host-side selector only: EPI_PLAIN with all 9 taps and the position-class bias table (BCLS)
 #define EPI_DGRAD_RES 9   // data gradient on the residual stream (its own compile-time epilogue: EPI_DGRAD's code stays what it was):
                        // modes MODE_DGRAD_RAW / MODE_DGRAD_SKIP
 
@@ -152,7 +153,11 @@ __device__ __forceinline__ float elu_f(float v) { return v > 0.f ? v : __expf(v)
 //   D            : lane l holds D[co = tile*16 + 4*(l>>4) + r][pixel l&15], r = 0..3
 // K order inside a 16-channel chunk is permuted: k-slot kk owns channels 4kk..4kk+3, MFMA j of the chunk
 // consumes channel 4kk+j, so each operand is ONE 16-byte load per lane per 4 MFMAs.
-template <int NT, int PXT, int WCO, int KS, int INMODE, int EPI, int NTP = NTAPS, bool DEEP = false>
+// BCLS (EPI_PLAIN with 9 taps only; the plain conv of the Theano statement, graphy/nodes/conv.py:71-83): p.bias is a table
+// [16 position classes][ncot * 16] -- bias + the border-indicator channel's taps that leave the image at a pixel of that class
+// (class = row above out | row below out << 1 | column left out << 2 | column right out << 3).  A compile-time form of its own:
+// the instantiations without it keep their code.
+template <int NT, int PXT, int WCO, int KS, int INMODE, int EPI, int NTP = NTAPS, bool DEEP = false, int BCLS = 0>
 __global__ __launch_bounds__(64 * PXT * WCO * KS) void iaf_conv_kernel(ConvP p) {
     extern __shared__ __attribute__((aligned(16))) f32x4 smem4[];
     constexpr int TM = 16 * PXT;
@@ -395,6 +400,10 @@ __global__ __launch_bounds__(64 * PXT * WCO * KS) void iaf_conv_kernel(ConvP p) 
             const int u = kh + i * KS;
             if (u >= NUNIT) continue;
             if (EPI == EPI_PLAIN) {
+                if constexpr (BCLS) {
+                    const int cls = (h == 0 ? 1 : 0) | (h == p.H - 1 ? 2 : 0) | (w == 0 ? 4 : 0) | (w == W - 1 ? 8 : 0);
+                    pbias[i] = *(const f32x4*)(p.bias + ((size_t)cls * p.ncot + cot0 + u) * 16 + 4 * kk);
+                } else
                 pbias[i] = *(const f32x4*)(p.bias + (cot0 + u) * 16 + 4 * kk);
                 if (p.res) {
                     const size_t cb = ((size_t)bimg * p.cout + (cot0 + u) * 16 + 4 * kk) * HW + pp;
@@ -785,4 +794,5 @@ __global__ __launch_bounds__(64 * PXT * WCO * KS) void iaf_conv_kernel(ConvP p) 
 
 typedef void (*conv_fn_t)(ConvP);
 // forms of the 9-tap plain conv (iaf_conv_bf3_plain_inst.hip: one picker per launch shape, iaf_pick_bf3p_*(nt, form))
-enum { BF3P_PLAIN, BF3P_DGRAD, BF3P_F16, BF3P_F16_DGRAD, BF3P_PRIOR, BF3P_PRIOR_F16, BF3P_S2, BF3P_DECONV };
+enum { BF3P_PLAIN, BF3P_DGRAD, BF3P_F16, BF3P_F16_DGRAD, BF3P_PRIOR, BF3P_PRIOR_F16, BF3P_S2, BF3P_DECONV,
+       BF3P_PLAIN_TH };      // BF3P_PLAIN with the position-class bias table of the Theano statement (BCLS)

@@ -400,6 +400,9 @@ struct WnBwdLayer {
     // dbrd = [nslab][4][cout_packed] partial gradients of the border channel's taps 1..4
     const float* dbrd; int variant;
     int skip;            // batched launch: this conv finished its own weight-norm backward already (a deconv2d)
+    // plain conv of the Theano statement (variant == PREP_PLAIN9_THEANO, wn_bwd_plain_theano_tile): dbrd = [nbrd][8][cout] partial
+    // gradients of the border channel's eight non-centre taps (iaf_border9_sum_kernel)
+    int nbrd;
 };
 
 template <int NCH>
@@ -753,6 +756,101 @@ __device__ __forceinline__ void wn_bwd_plain_tile(const WnBwdLayer& L, int tile,
 #pragma unroll
         for (int t = 0; t < MAXTAPS; ++t)
             L.dV[((size_t)t * n_in + cs + 16 * it) * n_out + o] = (e / n) * (dw[t][it] - (v[t][it] / n) * du);
+}
+
+// ... of the plain conv of the Theano statement (graphy/nodes/conv.py:122-260; prep_tile_plain_theano):
+//   K = e w / n,  n = ||w[o]|| over all n_in + 1 channels,  e = exp(3 s);  dK[o][c][8 - t] = dW[packed tap t][c][o] (the pack is flipped),
+//   dK of the border channel = the sums of dY over the pixels whose tap leaves the image (dbrd; its centre tap 0)
+//   ds = 3 sum dK K;  dw = (e/n)(dK - (w/n) (sum dK w/n));  db = sum_p dY.       dV is OIHW [cout][cin+1][3][3].
+// The border channel belongs to thread cs == 0.
+__global__ __launch_bounds__(256) void iaf_border9_sum_kernel(const float* __restrict__ dy, const unsigned short* __restrict__ tapmask,
+                                                             float* __restrict__ out, int P, int cout, int px_per_slab) {
+    __shared__ float part[4][8][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6;
+    const int p0 = blockIdx.y * px_per_slab, p1 = min(P, p0 + px_per_slab);
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c < cout)
+        for (int px = p0 + g; px < p1; px += 4) {
+            const unsigned m = tapmask[px];
+            if ((m & 0x1ffu) == 0x1ffu) continue;          // interior pixel (wave-uniform: the 64 lanes share the pixel)
+            const float d = dy[(size_t)px * cout + c];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += ((m >> (j < 4 ? j : j + 1)) & 1u) ? 0.f : d;
+        }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) part[g][j][threadIdx.x & 63] = acc[j];
+    __syncthreads();
+    if (g == 0 && c < cout) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            out[((size_t)blockIdx.y * 8 + j) * cout + c] = (part[0][j][threadIdx.x] + part[1][j][threadIdx.x]) + (part[2][j][threadIdx.x] + part[3][j][threadIdx.x]);
+    }
+}
+
+// (run-time chunk count, two passes over V and dW: one instantiation -- see prep_tile_plain_theano)
+__device__ __forceinline__ void wn_bwd_plain_theano_tile(const WnBwdLayer& L, int tile, float (*red)[16][17], float* s_n, float* s_dot) {
+    const int oo = threadIdx.x & 15, cs = threadIdx.x >> 4;
+    const int o = tile * 16 + oo;
+    const int n_in = L.cin, n_out = L.cout, nch = L.cin >> 4;
+    const float* wo = L.V + (size_t)o * (n_in + 1) * 9;
+    float vb[MAXTAPS], dwb[MAXTAPS];
+#pragma unroll
+    for (int t = 0; t < MAXTAPS; ++t) { vb[t] = 0.f; dwb[t] = 0.f; }
+    if (cs == 0) {
+#pragma unroll
+        for (int t = 0; t < MAXTAPS; ++t) {
+            vb[t] = wo[(size_t)n_in * 9 + (8 - t)];
+            if (t == 4) continue;
+            float a = 0.f;
+            for (int r = 0; r < L.nbrd; ++r) a += L.dbrd[((size_t)r * 8 + (t < 4 ? t : t - 1)) * n_out + o];
+            dwb[t] = a;
+        }
+    }
+    float dbs = 0.f;
+    for (int r = cs; r < L.nslab; r += 16) dbs += L.dbp[(size_t)r * L.cout_packed + o];
+    float ss = 0.f, dot = 0.f;
+    for (int it = 0; it < nch; ++it) {
+        const int ci = cs + 16 * it;
+#pragma unroll
+        for (int t = 0; t < MAXTAPS; ++t) {
+            const float v = wo[(size_t)ci * 9 + (8 - t)], d = L.dW[((size_t)t * n_in + ci) * L.cout_packed + o];
+            ss += v * v; dot += d * v;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < MAXTAPS; ++t) { ss += vb[t] * vb[t]; dot += dwb[t] * vb[t]; }
+    red[0][cs][oo] = ss; red[1][cs][oo] = dot; red[2][cs][oo] = dbs;
+    __syncthreads();
+    if (cs == 0) {
+        float a = 0.f, b = 0.f, c = 0.f;
+        for (int i = 0; i < 16; ++i) { a += red[0][i][oo]; b += red[1][i][oo]; c += red[2][i][oo]; }
+        const float n = sqrtf(a);
+        s_n[oo] = n;
+        s_dot[oo] = b / n;
+        L.dg[o] = 3.0f * expf(3.0f * L.g[o]) * b / n;
+        L.db[o] = c;
+    }
+    __syncthreads();
+    const float n = s_n[oo], du = s_dot[oo], e = expf(3.0f * L.g[o]);
+    float* dvo = L.dV + (size_t)o * (n_in + 1) * 9;
+    for (int it = 0; it < nch; ++it) {
+        const int ci = cs + 16 * it;
+#pragma unroll
+        for (int t = 0; t < MAXTAPS; ++t) {
+            const float v = wo[(size_t)ci * 9 + (8 - t)], d = L.dW[((size_t)t * n_in + ci) * L.cout_packed + o];
+            dvo[(size_t)ci * 9 + (8 - t)] = (e / n) * (d - (v / n) * du);
+        }
+    }
+    if (cs == 0) {
+#pragma unroll
+        for (int t = 0; t < MAXTAPS; ++t) dvo[(size_t)n_in * 9 + (8 - t)] = (e / n) * (dwb[t] - (vb[t] / n) * du);
+    }
+}
+
+__global__ __launch_bounds__(256) void iaf_wn_bwd_plain_theano_kernel(WnBwdLayer L) {
+    __shared__ float red[3][16][17];
+    __shared__ float s_n[16], s_dot[16];
+    wn_bwd_plain_theano_tile(L, blockIdx.x, red, s_n, s_dot);
 }
 
 __global__ __launch_bounds__(256) void iaf_wn_bwd_plain_kernel(WnBwdLayer L) {

@@ -46,6 +46,8 @@ struct PrepArgs {
 // run time, which the compiler lowered to vector loads of the 120-byte struct + a scratch copy (128 B per thread; 1216 B in
 // iaf_prep_kernel) with every pointer in VGPRs: 9 us of the 29 us batched launch (A/B on one box, 456.9 vs 465.6 us/step).
 #define PREP_PICK(arr, which) ((which) ? (arr)[1] : (arr)[0])
+#define PREP_PLAIN9 100          // PrepLayer.variant of a plain (unmasked, 9-tap) TF conv2d
+#define PREP_PLAIN9_THEANO 101   // ... of the plain conv of the Theano statement (graphy/nodes/conv.py:122-260): prep_tile_plain_theano
 
 // filter position (kh,kw) of live tap t: the 5 MADE-live taps (centre, right, then the row below), or all 9 row-major
 template <int NTP> __device__ __forceinline__ int tap_kh(int t) { return NTP == 9 ? t / 3 : ((t == 0 || t == 1) ? 1 : 2); }
@@ -460,8 +462,101 @@ __device__ __forceinline__ void prep_tile_theano(const PrepLayer& L, int gt, flo
     if constexpr (BF3) { if (L.wp3) prep_bf3_store<NCH>(L, gt, w3, s_scale); }
 }
 
+// The PLAIN conv of the Theano statement (graphy/nodes/conv.py:122-260 with pad_channel=True, l2norm=True, logscale=True):
+//   w is OIHW [n_out][n_in+1][3][3] (last input channel = border indicator, conv.py:71-83),
+//   K[o] = w[o] / sqrt(sum_{c <= n_in, a, b} w[o,c,a,b]^2) * exp(3 s[o])          -- NO epsilon (conv.py:162-164)
+//   and the conv is a TRUE convolution: filter position (a,b) meets the input at (dh,dw) = (1-a, 1-b).
+// The flip happens HERE: packed tap t (the launch's cross-correlation table: dh = t/3 - 1, dw = t%3 - 1) holds filter position 8 - t,
+// so forward, data gradient and weight gradient run the TF plain conv's kernels and tap tables unchanged.
+// The border channel never enters the GEMM.  Its centre tap counts in the norm only; its eight other taps are an addend that depends
+// on which neighbours of a pixel leave the image -- 16 position classes (row above out | row below out << 1 | column left out << 2 |
+// column right out << 3) -- and goes into the bias TABLE L.bias [16][ncot*16] = b + the class's addend (one load in the epilogue
+// instead of up to eight).  L.border [8][ncot*16]: the eight border weights themselves, in packed tap order without the centre.
+// L.V = w, L.g = s, L.b = b.
+// The chunk count is a RUN-TIME loop bound here (one instantiation, the weights read again in the second pass from L1 / L2) where
+// prep_tile keeps the tile in registers under sixteen instantiations: these four convs of a layer are prepared once per load(), not
+// once per step, and sixteen more fully unrolled 9-tap tiles cost the engine's translation unit more compile time than they save.
+__device__ __forceinline__ void prep_tile_plain_theano(const PrepLayer& L, int gt, float (*red)[17], float* s_scale) {
+    typedef __bf16 pb16x2 __attribute__((ext_vector_type(2)));
+    typedef float pf32x2 __attribute__((ext_vector_type(2)));
+    typedef unsigned pu32x4 __attribute__((ext_vector_type(4)));
+    const float* __restrict__ Wt = L.V[0];
+    const int oo = threadIdx.x & 15, cs = threadIdx.x >> 4;
+    const int o = gt * 16 + oo;
+    const int n_in = L.cin, nch = L.nchunk;
+    const float sval = L.g[0][o], bval = L.b[0][o];
+    const float* wo = Wt + (size_t)o * (n_in + 1) * 9;
+    float wb[MAXTAPS];     // border channel by PACKED tap (thread cs == 0 accounts for it in the norm, centre included)
+#pragma unroll
+    for (int t = 0; t < MAXTAPS; ++t) wb[t] = wo[(size_t)n_in * 9 + (8 - t)];
+    float ss = 0.f;
+    for (int it = 0; it < nch; ++it) {
+        const float* q = wo + (size_t)(cs + 16 * it) * 9;
+#pragma unroll
+        for (int t = 0; t < MAXTAPS; ++t) ss += q[t] * q[t];
+    }
+    if (cs == 0) {
+#pragma unroll
+        for (int t = 0; t < MAXTAPS; ++t) ss += wb[t] * wb[t];
+    }
+    red[cs][oo] = ss;
+    __syncthreads();
+    if (cs == 0) {
+        float tot = 0.f;
+        for (int i = 0; i < 16; ++i) tot += red[i][oo];
+        s_scale[oo] = expf(3.0f * sval) / sqrtf(tot);         // (an all-zero filter: NaN, as the reference's own division)
+    }
+    __syncthreads();
+    const float scale = s_scale[oo];
+    {   // thread cs writes the bias of position class cs
+        float a = bval, mine = 0.f;        // (static indices into wb only: a run-time index would put it in scratch)
+#pragma unroll
+        for (int t = 0; t < MAXTAPS; ++t) {
+            if (t == 4) continue;
+            const int dh = t / 3 - 1, dw = t % 3 - 1;
+            const bool out = (dh < 0 && (cs & 1)) || (dh > 0 && (cs & 2)) || (dw < 0 && (cs & 4)) || (dw > 0 && (cs & 8));
+            if (out) a += wb[t] * scale;
+            if ((t < 4 ? t : t - 1) == cs) mine = wb[t] * scale;
+        }
+        L.bias[((size_t)cs * L.ncot + gt) * 16 + oo] = a;
+        if (cs < MAXTAPS - 1 && L.border) L.border[(size_t)cs * (L.ncot * 16) + gt * 16 + oo] = mine;
+    }
+    const int kk = cs >> 2, jj = cs & 3;
+    if (L.wp || L.wpt)
+        for (int it = 0; it < nch; ++it) {
+            const float* q = wo + (size_t)(cs + 16 * it) * 9;
+#pragma unroll
+            for (int t = 0; t < MAXTAPS; ++t) {
+                const float x = q[8 - t] * scale;
+                if (L.wp) L.wp[((((size_t)it * MAXTAPS + t) * L.ncot + gt) * 64 + kk * 16 + oo) * 4 + jj] = x;
+                // dgrad operand, as in prep_tile (the border channel carries no data gradient)
+                if (L.wpt) L.wpt[((((size_t)gt * MAXTAPS + t) * nch + it) * 64 + (oo >> 2) * 16 + cs) * 4 + (oo & 3)] = x;
+            }
+        }
+    if (L.wp3 && !(nch & 1)) {      // the bf16x3 pack in the fragment's own mapping (prep_bf3_load / prep_bf3_store): a unit = (c_in pair, tap)
+        const int lane = threadIdx.x & 63, quarter = threadIdx.x >> 6, kk3 = lane >> 4;       // (lane & 15 == oo)
+        const int nunit = (nch >> 1) * MAXTAPS;
+        for (int u = quarter; u < nunit; u += 4) {
+            const int pair = u / MAXTAPS, t = u - pair * MAXTAPS;
+            const float* q = wo + (size_t)(pair * 32 + 8 * kk3) * 9 + (8 - t);
+            pu32x4 ph, pm, pl;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const pf32x2 x = {q[(2 * k) * 9] * scale, q[(2 * k + 1) * 9] * scale};
+                const pb16x2 hb = __builtin_convertvector(x, pb16x2);
+                const pf32x2 r1 = x - __builtin_convertvector(hb, pf32x2);
+                const pb16x2 mb = __builtin_convertvector(r1, pb16x2);
+                const pf32x2 r2 = r1 - __builtin_convertvector(mb, pf32x2);
+                const pb16x2 lb = __builtin_convertvector(r2, pb16x2);
+                ph[k] = __builtin_bit_cast(unsigned, hb); pm[k] = __builtin_bit_cast(unsigned, mb); pl[k] = __builtin_bit_cast(unsigned, lb);
+            }
+            pu32x4* dst = (pu32x4*)L.wp3 + (((size_t)(pair * MAXTAPS + t) * L.ncot + gt) * 3) * 64 + lane;
+            dst[0] = ph; dst[64] = pm; dst[128] = pl;
+        }
+    }
+}
+
 #define PREP_MAXI 16   // n_in <= 256
-#define PREP_PLAIN9 100   // PrepLayer.variant of a plain (unmasked, 9-tap) TF conv2d
 // fast_tile / fast_floats: the launch's dynamic LDS (prep_tile_fast) and its size in floats (0: none)
 template <int DUMMY = 0>
 __device__ __forceinline__ void prep_dispatch(const PrepLayer& L, int gt, float (*red)[17], float* s_scale, float* fast_tile = nullptr,
@@ -537,6 +632,10 @@ __global__ __launch_bounds__(256) void iaf_prep_plain_kernel(const PrepLayer* __
     __shared__ float s_scale[16];
     const PrepLayer& L = layers[tile2layer ? __builtin_amdgcn_readfirstlane(tile2layer[blockIdx.x]) : 0];
     const int gt = blockIdx.x - L.tile_begin;
+    if (L.variant == PREP_PLAIN9_THEANO) {
+        prep_tile_plain_theano(L, gt, red, s_scale);
+        return;
+    }
     switch (L.nchunk) {
         case 1: prep_tile<1, MAXTAPS>(L, gt, red, s_scale); break;
         case 2: prep_tile<2, MAXTAPS>(L, gt, red, s_scale); break;

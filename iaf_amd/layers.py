@@ -636,12 +636,16 @@ class WNConv2d(object):
 
     def __init__(self, n_in, n_out, ar_mask=None, theano=False, flipmask=False):
         """ar_mask: None = plain conv2d; False / True = ar_conv2d with zerodiagonal=False / True (layers.py:144-154).
-        theano=True (masked only): the Theano statement, N.ar.conv2d (graphy/nodes/ar.py:200-375), optionally flipmask;
-        prepare() then takes (w OIHW [n_out, n_in+1, 3, 3], s, b)."""
+        theano=True: the Theano statement -- with ar_mask False / True the masked conv N.ar.conv2d (graphy/nodes/ar.py:200-375),
+        optionally flipmask; with ar_mask=None the plain conv N.conv.conv2d (graphy/nodes/conv.py:122-260: pad_channel, l2norm,
+        logscale; iaf_conv3x3_create_theano), whose backward returns dV in OIHW.  prepare() then takes
+        (w OIHW [n_out, n_in+1, 3, 3], s, b)."""
         self.n_in, self.n_out, self.ar_mask, self.theano = int(n_in), int(n_out), ar_mask, bool(theano)
-        if theano:
-            if ar_mask is None:
-                raise ValueError("theano=True is the masked conv N.ar.conv2d: pass ar_mask=False/True (zerodiagonal)")
+        if theano and ar_mask is None:
+            if flipmask:
+                raise ValueError("flipmask belongs to the masked conv N.ar.conv2d: pass ar_mask=False/True (zerodiagonal)")
+            self._own = _capi.Handle("iaf_conv3x3_create_theano", self.n_in, self.n_out)
+        elif theano:
             self._own = _capi.Handle("iaf_conv3x3_create_masked_theano", self.n_in, self.n_out, 1 if ar_mask else 0, 1 if flipmask else 0)
         elif ar_mask is None:
             self._own = _capi.Handle("iaf_conv3x3_create", self.n_in, self.n_out)
@@ -700,6 +704,14 @@ class WNConv2d(object):
 
     def runs_f16x2(self, B, H, W):
         return bool(_capi.lib().iaf_conv3x3_runs_f16x2(self._h, int(B), int(H), int(W)))
+
+    def dgrad_runs_bf16x3(self, B, H, W):
+        """whether backward() at this size runs its data gradient on the split products (iaf_conv3x3_dgrad_runs_bf16x3)"""
+        return bool(_capi.lib().iaf_conv3x3_dgrad_runs_bf16x3(self._h, int(B), int(H), int(W)))
+
+    def set_dgrad_tuning(self, nt, ppw, wco, ks):
+        """pin the data gradient's split-product launch shape (after set_training; nt = 0: the size rule again)"""
+        _capi.check(_capi.lib().iaf_conv3x3_set_dgrad_tuning(self._h, nt, ppw, wco, ks))
 
     def set_packs(self, f32=True, bf16x3=True, f16x2=True):
         """which weight packs the prep launches of this plain conv keep up to date (iaf_conv3x3_set_packs; default: all three, 14 bytes
@@ -1198,7 +1210,7 @@ class ConvPrepBatch(object):
         """vgb_list: one (V, g, b) tuple of device tensors per conv, in construction order."""
         tens = []
         for c, (V, g, b) in zip(self.convs, vgb_list):
-            _check_act(V, "V", (3, 3, c.n_in, c.n_out))
+            _check_act(V, "V", (c.n_out, c.n_in + 1, 3, 3) if c.theano else (3, 3, c.n_in, c.n_out))     # (theano: (w OIHW, s, b))
             _check_act(g, "g", (c.n_out,))
             _check_act(b, "b", (c.n_out,))
             tens += [V, g, b]
@@ -1335,6 +1347,28 @@ def ar_conv2d_theano(name, n_in, n_out, size_kernel=(3, 3), zerodiagonal=True, f
         return conv(h)[0]
 
     return _Struct(f=f, w=w, conv=conv, postup=lambda updates, w: updates)
+
+
+def conv2d_theano(name, n_in, n_out, size_kernel=(3, 3), zeroinit=False, downsample=1, upsample=1, pad_channel=True, w=None):
+    """Mirror of N.conv.conv2d(name, n_in, n_out, size_kernel, ..., w=w) of the Theano path (graphy/nodes/conv.py:122-260) with its
+    defaults border_mode 'valid' + pad_channel=True, l2norm=True, logscale=True: the plain conv around the IAF step (up_conv1/2,
+    down_conv1/2 of models.cvae_layer).  Returns a callable struct f(h, w) -> conv output (NCHW device tensors) with f.conv the
+    WNConv2d(theano=True) behind it (f.conv(h, elu_input=..., residual=..., split=...) for the fused forms); weights w[name + '_w']
+    OIHW [n_out, n_in + 1, 3, 3], '_s', '_b'."""
+    if tuple(size_kernel) != (3, 3):
+        raise _capi.UnsupportedError("the gfx950 engine states N.conv.conv2d for 3x3 kernels (what models.cvae_layer uses)")
+    if downsample != 1 or upsample != 1:
+        raise _capi.UnsupportedError("N.conv.conv2d with downsample / upsample != 1 (the downsampling layer's strided convs) is not built "
+                                     "for the Theano statement")
+    if not pad_channel:
+        raise _capi.UnsupportedError("N.conv.conv2d with pad_channel=False is not built: the reference's layer uses the border channel")
+    conv = WNConv2d(n_in, n_out, theano=True)
+
+    def f(h, w):
+        conv.prepare(w[name + "_w"], w[name + "_s"], w[name + "_b"])
+        return conv(h)[0]
+
+    return _Struct(f=f, conv=conv, name=name, n_in=int(n_in), n_out=int(n_out), w=w)
 
 
 def _is_elu(nl):

@@ -3,8 +3,11 @@ BASELINE names -- 'down_iaf2_nl' (configs 0-2, 4) and 'up_iaf2_nl' (config 3) --
 of two IAF steps on one context, posterior_conv1 with the plain ordering and posterior_conv2 with the flipped one, both log-determinants
 added to logqs -- the construction of the IAF paper, in which no latent stays first in every ordering.
 
-Boundary: the plain Theano convs around the IAF step (up_conv1/2, down_conv1/2: graphy/nodes/conv.py) are out
-of scope; this wrapper takes THEIR OUTPUTS in the reference's channel order and returns what the next conv consumes:
+Two classes.  CVAELayerIAF is the IAF part BETWEEN the plain Theano convs (up_conv1/2, down_conv1/2: graphy/nodes/conv.py:122-260):
+it takes THEIR OUTPUTS in the reference's channel order and returns what the next conv consumes.  CVAELayer (at the end of this
+file) is the whole models.cvae_layer with downsample=False: it owns a CVAELayerIAF and the four convs (layers.WNConv2d(theano=True),
+iaf_conv3x3_create_theano), loads a Theano weight dict and runs up / down_q / down_p and the two-phase backward on the device.
+The channel layouts between the convs and the IAF part:
 
     up_conv1 output    [h_det (n_h) | qz_mean (n_z) | qz_logsd (n_z) | context (n_h)]            models.py:139-143, 164/181
     down_conv1 output  [h_det (n_h) | pz_mean (n_z) | pz_logsd (n_z) || rz_mean | rz_logsd | down_context (n_h)]  :273-279, 296-297
@@ -49,7 +52,8 @@ import torch
 from . import _capi
 from .distributions import gaussian_diag_logps_logsd
 from .iaf_layer import gaussian_sample
-from .layers import ARStack, PrepBatch, ResnetARStack, kl_free_bits, split, theano_stack, _check_act, _ptr, _stream
+from .layers import (ARStack, ConvPrepBatch, PrepBatch, ResnetARStack, WNConv2d, kl_free_bits, split, theano_stack, _check_act, _ptr,
+                     _stream)
 
 POSTERIORS = ("down_iaf2_nl", "up_iaf2_nl", "down_iaf2_nl2", "down_iaf2_deep")
 PRIORS = ("diag", "made")
@@ -433,3 +437,117 @@ class CVAELayerIAF(object):
                 _ptr(dz0), _ptr(st["z0"]), _ptr(st["qz_mean"]), _ptr(G), _ptr(dctx), _ptr(d_up_c), _ptr(d_uc1), B, n_h, n_z, H * W,
                 _stream()))
         return dict(d_up_conv1=d_uc1, d_down_conv1=d_dc1, grads={pre + k: v for k, v in grads.items()})
+
+
+class CVAELayer(object):
+    """models.cvae_layer(name, prior, posterior, n_h1 = n_h2 = n_h, n_z, depth_ar, downsample=False, nl='elu', ..., w) (models.py:14-345)
+    on the device: the four plain Theano convs (graphy/nodes/conv.py:122-260; layers.WNConv2d(theano=True)) around a CVAELayerIAF,
+    which stays what it is.  Conv widths (models.py:25-29, 59-108):
+
+        <name>_up_conv1_1    n_h -> 2 n_h + 2 n_z
+        <name>_up_conv2      n_h -> n_h                      ('up_iaf2_nl': n_h + n_z -> n_h)
+        <name>_down_conv1    n_h -> 2 n_h + 4 n_z            ('up_iaf2_nl': n_h + 2 n_z;  prior 'made': 3 n_h + 2 n_z)
+        <name>_down_conv2_1  n_h + n_z -> n_h
+
+    The elu in front of every conv and the `input + 0.1 *` behind up_conv2 / down_conv2_1 are fused into the conv launches.  Launches
+    of up() + down_q(): four convs + the IAF part's own (see CVAELayerIAF) + ONE copy: the IAF part hands h_det to up_conv2 as a
+    contiguous copy of the first n_h channels of up_conv1's output ('down_*' posteriors; 'up_iaf2_nl': torch.cat([h_det, z])), a conv
+    input being a whole tensor.  Nothing synchronises with the host, so after a warm-up up() + down_q() capture into one graph.
+    Channel counts must be multiples of 16 (n_h at most 240 so that n_h + n_z <= 256)."""
+    CONVS = ("_up_conv1_1", "_up_conv2", "_down_conv1", "_down_conv2_1")
+
+    def __init__(self, name, n_h, n_z, depth_ar, posterior="down_iaf2_nl", prior="diag", flipmask=False, kl_min=0.0, downsample=False):
+        if downsample:
+            raise _capi.UnsupportedError("downsample=True is not built: the two strided convs (up_conv1_2 / up_conv3 with downsample 2, "
+                                         "down_conv2_2 / down_conv3 with upsample 2 through depool2d_split) and the 'nn' resampling of "
+                                         "the residual are missing for the Theano statement")
+        self.iaf = CVAELayerIAF(name, n_h, n_z, depth_ar, posterior=posterior, flipmask=flipmask, kl_min=kl_min, prior=prior)
+        self.name, self.n_h, self.n_z, self.posterior, self.prior = name, int(n_h), int(n_z), posterior, prior
+        n_h, n_z = self.n_h, self.n_z
+        if prior == "made":
+            n_down1 = 3 * n_h + 2 * n_z                                               # models.py:38
+        else:
+            n_down1 = n_h + 2 * n_z if posterior == "up_iaf2_nl" else 2 * n_h + 4 * n_z
+        self.widths = {"_up_conv1_1": (n_h, 2 * n_h + 2 * n_z), "_up_conv2": (n_h + n_z if posterior == "up_iaf2_nl" else n_h, n_h),
+                       "_down_conv1": (n_h, n_down1), "_down_conv2_1": (n_h + n_z, n_h)}
+        self.convs = {nm: WNConv2d(a, b, theano=True) for nm, (a, b) in self.widths.items()}
+        self._prep = ConvPrepBatch([self.convs[nm] for nm in self.CONVS])
+        self._w, self._st, self._grads, self.training = None, {}, {}, False
+
+    def set_training(self, on=True):
+        """keep what the backward needs (call load() again afterwards: the data-gradient packs are written by the next prepare)"""
+        self.iaf.set_training(on)
+        for c in self.convs.values():
+            c.set_training(on)
+        self.training = bool(on)
+
+    def load(self, w):
+        """w: the reference's parameter dict.  Reads <name>_up_conv1_1_*, <name>_up_conv2_*, <name>_down_conv1_*, <name>_down_conv2_1_*
+        (w OIHW [n_out, n_in + 1, 3, 3], s, b; the four convs prepare in ONE launch) and hands the rest to the IAF part."""
+        self._w = {nm: (w[self.name + nm + "_w"], w[self.name + nm + "_s"], w[self.name + nm + "_b"]) for nm in self.CONVS}
+        self._prep.run([self._w[nm] for nm in self.CONVS])
+        self.iaf.load(w)
+
+    def up(self, input, eps=None):
+        """models.py:138-194: input [B, n_h, H, W] -> output [B, n_h, H, W] (eps [B, n_z, H, W]: 'up_iaf2_nl' only)"""
+        _check_act(input, "input")
+        h = self.convs["_up_conv1_1"](input, elu_input=True)[0]
+        hu = self.iaf.up(h, eps=eps)
+        out = self.convs["_up_conv2"](hu, elu_input=True, residual=input)[0]
+        self._st.update(up_input=input, up_conv2_in=hu)
+        return out
+
+    def down_q(self, input, eps=None):
+        """models.py:201-328: input [B, n_h, H, W], eps [B, n_z, H, W] -> dict(output [B, n_h, H, W], kl, kl_sum, obj_kl, z) (kl is None
+        on the training path of 'down_iaf2_nl', as in CVAELayerIAF.down_q)"""
+        _check_act(input, "input")
+        h = self.convs["_down_conv1"](input, elu_input=True)[0]
+        d = self.iaf.down_q(h, eps=eps)
+        out = self.convs["_down_conv2_1"](d["h"], elu_input=True, residual=input)[0]
+        self._st.update(down_input=input, down_conv2_in=d["h"])
+        return dict(output=out, kl=d["kl"], kl_sum=d["kl_sum"], obj_kl=d["obj_kl"], z=d["z"])
+
+    def down_p(self, input, eps, **inverse_options):
+        """models.py:330-359: a sample of the prior pushed down.  inverse_options: CVAELayerIAF.down_p's (exact, max_sweeps, ...)"""
+        _check_act(input, "input")
+        h = self.convs["_down_conv1"](input, elu_input=True)[0]
+        hp = self.iaf.down_p(h, eps, **inverse_options)
+        return self.convs["_down_conv2_1"](hp, elu_input=True, residual=input)[0]
+
+    def _conv_backward(self, nm, x, dy, dy_scale, dx_residual):
+        V, s, _ = self._w[nm]
+        dxs, dV, ds, db = self.convs[nm].backward(x, [dy], V, s, elu_input=True, dy_scale=dy_scale, dx_residual=dx_residual)
+        self._grads.update({self.name + nm + "_w": dV, self.name + nm + "_s": ds, self.name + nm + "_b": db})
+        return dxs[0]
+
+    def backward_down(self, d_down_out, d_obj=None):
+        """First phase of T.grad of  <d_up_out, up()> + <d_down_out, down_q()['output']> + <d_obj, obj_kl>: everything that does not
+        need d_up_out -- down_conv2_1, the IAF part, down_conv1.  Returns d_down_input.  (The cotangent of up()'s output exists only
+        once the layers above have run THEIR backward: backward_up comes second.)  d_obj as CVAELayerIAF.backward: a number with free
+        bits, [B] without, None = ones."""
+        if self.posterior == "up_iaf2_nl":
+            raise _capi.UnsupportedError("the whole-layer backward of 'up_iaf2_nl' is not built: its IAF step sits in the up pass, so the "
+                                         "step's gradient needs d_up_out (use CVAELayerIAF.backward between the convs)")
+        if not self.training or "down_conv2_in" not in self._st:
+            raise RuntimeError("backward_down() follows up() and down_q() in training mode")
+        _check_act(d_down_out, "d_down_out", tuple(self._st["down_input"].shape))
+        d_h = self._conv_backward("_down_conv2_1", self._st["down_conv2_in"], d_down_out, 0.1, None)
+        bw = self.iaf.backward(d_h, d_obj=d_obj, d_up=None)
+        self._grads.update(bw["grads"])
+        self._st["d_up_conv1"] = bw["d_up_conv1"]           # its h_det channels (zero so far) are filled by backward_up
+        return self._conv_backward("_down_conv1", self._st["down_input"], bw["d_down_conv1"], 1.0, d_down_out)
+
+    def backward_up(self, d_up_out):
+        """Second phase: up_conv2, then up_conv1 on [d h_det | what backward_down left for qz_mean, qz_logsd, context].  Returns
+        d_up_input.  One strided torch copy puts d h_det into the first n_h channels of d_up_conv1."""
+        if "d_up_conv1" not in self._st:
+            raise RuntimeError("backward_up() follows backward_down()")
+        _check_act(d_up_out, "d_up_out", tuple(self._st["up_input"].shape))
+        d_hu = self._conv_backward("_up_conv2", self._st["up_conv2_in"], d_up_out, 0.1, None)
+        d_uc1 = self._st.pop("d_up_conv1")
+        d_uc1.narrow(1, 0, self.n_h).copy_(d_hu)
+        return self._conv_backward("_up_conv1_1", self._st["up_input"], d_uc1, 1.0, d_up_out)
+
+    def grads(self):
+        """every gradient of the last backward_down + backward_up, keyed like the reference's w (the IAF part's included)"""
+        return dict(self._grads)

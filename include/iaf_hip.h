@@ -652,6 +652,30 @@ int iaf_conv3x3_create_masked(iaf_conv3x3_t** out, int n_in, int n_out, int zero
  * V = <name>_w OIHW [n_out][n_in+1][3][3] (border-indicator channel last), g = <name>_s (applied as exp(3 s)), b = <name>_b.
  * Channels must be multiples of 16.  Forward only. */
 int iaf_conv3x3_create_masked_theano(iaf_conv3x3_t** out, int n_in, int n_out, int zerodiagonal, int flipmask);
+/* The PLAIN conv of the Theano path: N.conv.conv2d(name, n_in, n_out, (3,3), w=w) with pad_channel=True, border 'valid',
+ * l2norm=True, logscale=True, no down- / upsampling (graphy/nodes/conv.py:122-260; up_conv1/2 and down_conv1/2 of
+ * models.cvae_layer).  Same object type and calls as the plain conv:
+ *   iaf_conv3x3_prepare / iaf_conv3x3_prep_batch_run take V = <name>_w OIHW [n_out][n_in+1][3][3] (border-indicator channel
+ *     last), g = <name>_s, b = <name>_b:  K[o] = w[o] / sqrt(sum over all n_in + 1 channels of w[o]^2) * exp(3 s[o]), NO epsilon
+ *     (conv.py:162-164; an all-zero filter yields NaN as in the reference).  The filter is flipped at pack time (a true
+ *     convolution), the border channel never enters the GEMM: its eight non-centre taps become a per-pixel addend that depends
+ *     only on which neighbours of the pixel leave the image (16 position classes), kept as a bias table [16][n_out].
+ *   iaf_conv3x3_forward keeps its whole contract (concat, elu_input, residual + 0.1 y, split store).
+ *   iaf_conv3x3_set_training / iaf_conv3x3_backward work: dV is OIHW [n_out][n_in+1][3][3] including the border channel (its
+ *     centre tap 0 before the norm's projection), dg = ds, db.
+ * n_in and n_out must be multiples of 16 with n_in <= 256.  Precision: IAF_PRECISION_BF16X3 (default where n_in % 32 == 0) or
+ * IAF_PRECISION_F32.  These answer IAF_ERR_UNSUPPORTED for such a conv, before any other answer: generic channel counts (at
+ * create), iaf_conv3x3_set_precision(IAF_PRECISION_F16X2), iaf_conv3x3_set_packs with IAF_PACK_F16X2 alone (and
+ * iaf_conv3x3_runs_f16x2 answers 0), iaf_conv3x3_forward_stride2, iaf_conv3x3_forward_deconv, iaf_conv3x3_prepare_deconv,
+ * iaf_conv3x3_forward_prior_sample, iaf_conv3x3_forward_hdet, iaf_conv3x3_set_defer_weightnorm /
+ * iaf_conv3x3_wn_bwd_batch_create (the deferred weight-norm batch), iaf_conv3x3_autotune and iaf_conv3x3_autotune_backward. */
+int iaf_conv3x3_create_theano(iaf_conv3x3_t** out, int n_in, int n_out);
+/* The data gradient of iaf_conv3x3_backward (plain convs, TF or Theano statement): 1 if a call at this size runs the split products;
+ * and a pin of its split-product launch shape (nt, ppw, wco, ks as iaf_conv3x3_set_tuning's negative-nt form reports them; nt = 0: back
+ * to the size rule, which takes the split products from 4096 pixels on).  The pin follows iaf_conv3x3_set_training, which resets it;
+ * IAF_ERR_UNSUPPORTED where the conv has no transposed split pack (n_out % 32 != 0) or the shape is not compiled. */
+int iaf_conv3x3_dgrad_runs_bf16x3(iaf_conv3x3_t* c, int B, int H, int W);
+int iaf_conv3x3_set_dgrad_tuning(iaf_conv3x3_t* c, int nt, int ppw, int wco, int ks);
 int iaf_conv3x3_destroy(iaf_conv3x3_t* c);
 /* weight normalisation + packing (one launch); call again whenever V/g/b change */
 int iaf_conv3x3_prepare(iaf_conv3x3_t* c, const float* V, const float* g, const float* b, void* stream);
